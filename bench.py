@@ -14,7 +14,15 @@ N=8, config 4 as BASELINE.json states it): "scaling": "strong".  `value` = parti
 iterations of MCMC steps x global particles, the reference's `calls` bookkeeping, mcmc.py:89) / wall time, user
 likelihood included, inputs resident in HBM.  `--particles-per-gpu P` overrides the shard size (global = P x N).
 
-Also in the JSON line:
+A plain run does only what `value` and `ms_per_step` need: it builds the Sampler, runs the prior-draw iterations, the W
+warm-up and the K timed steps, and prints the line.  `--dump-outputs DIR` then writes what the last timed step handed its
+caller (the current state Sampler.sample returns: u, x, logl on a fixed sample of rows, and the iteration's scalars) as
+float64 .npy files, so that two builds can be compared output for output on the same seeded inputs.
+
+With --full the JSON line also carries (each leg can be switched off by its --no-* option):
+  digest, logz, whole_run
+                the run continued, untimed, to the reference's stopping rule; whole_run_warm repeats it in the same process.
+  comm          (N > 1) what the sharded run exchanged between the ranks, and every rank's time per phase.
   roofline      the reweight reduction kernel (north_star's named kernel) on a 1.07 GB synthetic history
                 (outside the 256 MB Infinity Cache): algorithmic 16 B per historical particle /
                 HIP-event average launch duration, against 8 TB/s nominal AND against the streaming-read / copy ceilings
@@ -161,6 +169,29 @@ def cpu_baseline(budget_s=5.0):
             "phase_seconds": {k: round(v, 2) for k, v in s.timing.items()}}
 
 
+DUMP_ROWS = 262_144         # particle rows written by --dump-outputs: 22 doubles a row at d = 10, about 46 MB in all
+
+
+def dump_outputs(s, out_dir, sharded, rank):
+    """Sampler.sample's current state after the last timed step as DIR/<key>.npy (float64): u, x, logl (all ranks' rows in slot
+    order) on a fixed, seeded sample of DUMP_ROWS rows whose indices go to rows.npy, and every scalar of the iteration.
+    Collective when sharded (the rows of every rank are gathered); rank 0 writes."""
+    cur = s.state.get_current()
+    rows = {k: cur.pop(k) for k in ("u", "x", "logl")}
+    if sharded:
+        rows = {k: s.state.comm.gather_rows(v) for k, v in rows.items()}
+    if rank != 0:
+        return
+    n = rows["logl"].shape[0]
+    keep = np.arange(n) if n <= DUMP_ROWS else np.sort(np.random.default_rng(0).choice(n, DUMP_ROWS, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    out = {k: v[keep] for k, v in rows.items()}
+    out["rows"] = keep
+    out.update({k: v for k, v in cur.items() if k not in ("assignments", "blobs") and v is not None})
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.asarray(v, dtype=np.float64))
+
+
 def main():
     # everything except the final JSON line goes to stderr: RCCL prints a version banner on stdout at communicator
     # creation, and the driver expects exactly one line there
@@ -193,7 +224,13 @@ def main():
                     help="run with the Sampler's default clustering=True (SURVEY 8d fixes clustering=False for config 4: the "
                          "headline line is produced without this flag; rehearsals use it to walk the clustered code path)")
     ap.add_argument("--roofline-only", action="store_true", help="only the reweight-kernel microbench (for rocprofv3 --pmc)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the legs beside the headline (see the module docstring); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state the last timed step returned as DIR/<name>.npy (float64, about 46 MB)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.roofline_only:
         emit({"roofline": reweight_roofline(int(os.environ.get("LOCAL_RANK", "0")), a.roofline_rows)})
         return
@@ -285,9 +322,11 @@ def main():
     sync()
     t_run0 = t_make0          # `whole_run` is timed from BEFORE the Sampler's construction: its parallel start-up begins there
     dt, steps_t, beta_t = timed(s)
+    if a.dump_outputs:
+        dump_outputs(s, a.dump_outputs, use_dist, rank)
     startup = s.startup_breakdown
     comm_block = None
-    if use_dist:
+    if use_dist and a.full:
         # what the sharded run actually did between the ranks during everything up to here (initialisation, warm-up, timed steps)
         st = s.state.ctx.comm_stats()
         its = max(1, len(s.state._scalars["steps"]))
@@ -320,7 +359,7 @@ def main():
              "timed_iteration_range_of_run": [n_before + 1, n_before + len(steps_t)],
              "beta_range": [float(beta_t.min()), float(beta_t.max())],
              "reweight_evals_per_iteration": round(s._core.reweighter.n_evals / max(1, len(s.state._scalars["beta"])), 1)}
-    if not a.no_finish:
+    if a.full and not a.no_finish:
         # run on to the reference's stopping rule for the evidence (untimed)
         core = s._core
         core.n_total = n_total
@@ -422,7 +461,7 @@ def main():
     if comm_block is not None:
         out["comm"] = comm_block
     out["config"]["callbacks"] = "torch-ROCm tensor callbacks (the drop-in contract: prior20, rosenbrock_torch)"
-    if not a.no_hip_callbacks:
+    if a.full and not a.no_hip_callbacks:
         # same workload, same seed, same protocol, with the two callbacks written as HIP device functions and compiled
         # into the Metropolis kernel: a step is 4 launches instead of ~16.  Reported beside `value`, never as `value`.
         try:
@@ -441,7 +480,7 @@ def main():
             torch.cuda.empty_cache()
         except Exception as e:       # no hipcc on the box, ...
             out["hip_callbacks"] = {"value": None, "error": f"{type(e).__name__}: {e}"[:300]}
-    if world > 1 and a.particles_per_gpu <= 0 and not a.no_weak:
+    if a.full and world > 1 and a.particles_per_gpu <= 0 and not a.no_weak:
         # the weak-scaling figure beside the headline: 1 048 576 particles PER GPU, same protocol
         try:
             s = None
@@ -456,7 +495,7 @@ def main():
             torch.cuda.empty_cache()
         except Exception as e:
             out["weak_scaling"] = {"value": None, "error": f"{type(e).__name__}: {e}"[:300]}
-    if rank == 0:
+    if rank == 0 and a.full:
         if not a.no_roofline:
             out["roofline"] = reweight_roofline(local_rank, a.roofline_rows)
         if not a.no_cpu_baseline and world == 1:       # the CPU baseline belongs to the N = 1 line only

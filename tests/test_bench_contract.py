@@ -5,6 +5,8 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -82,7 +84,7 @@ def test_committed_profiles_are_self_consistent():
 def test_bench_cli_defaults():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup"):
+    for flag in ("--gpus", "--steps", "--warmup", "--full", "--dump-outputs"):
         assert flag in out.stdout + out.stderr          # bench.py routes everything but the JSON line to stderr
 
 
@@ -103,7 +105,7 @@ def test_bench_two_ranks_rehearsal_on_one_gpu(tmp_path):
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
     env = dict(os.environ, TEMPEST_AMD_BENCH_REHEARSAL="1", TEMPEST_AMD_P2P_TIMEOUT="60")
-    common = ["--steps", "2", "--warmup", "1", "--particles", "32768", "--no-roofline", "--no-cpu-baseline"]
+    common = ["--full", "--steps", "2", "--warmup", "1", "--particles", "32768", "--no-roofline", "--no-cpu-baseline"]
     two = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                           "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2"] + common,
                          capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
@@ -141,7 +143,7 @@ def test_bench_four_ranks_rehearsal_with_clustering_on_one_gpu():
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
     env = dict(os.environ, TEMPEST_AMD_BENCH_REHEARSAL="1", TEMPEST_AMD_P2P_TIMEOUT="60")
-    common = ["--steps", "2", "--warmup", "1", "--particles", "16384", "--no-roofline", "--no-cpu-baseline", "--clustering",
+    common = ["--full", "--steps", "2", "--warmup", "1", "--particles", "16384", "--no-roofline", "--no-cpu-baseline", "--clustering",
               "--no-hip-callbacks", "--no-weak", "--no-second-run"]
     four = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr",
                            "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "4"] + common,
@@ -165,6 +167,43 @@ def test_bench_four_ranks_rehearsal_with_clustering_on_one_gpu():
     assert abs(d1["iterations_total"] - d4["iterations_total"]) <= 2
     assert abs(d1["logz"] - d4["logz"]) < 0.4, (d1["logz"], d4["logz"])
     assert abs(d4["logz"] - d4["analytic_logz"]) < 1.2 and abs(d1["logz"] - d1["analytic_logz"]) < 1.2
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full) prints the headline fields and none of the legs that take runs of their own; --steps sets the
+    number of timed steps; --dump-outputs writes the state the last timed step returned as float64 .npy files (within 64 MB),
+    and a second run with the same arguments writes the same arrays."""
+    torch = pytest.importorskip("torch")
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    lines = []
+    for run in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                              "--particles", "32768", "--dump-outputs", str(tmp_path / run)],
+                             capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines.append(json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]))
+    d = lines[0]
+    assert d["steps"] == 3 and d["timed_iterations"] == 3 and d["warmup"] == 1
+    first, last = d["timed_iteration_range_of_run"]
+    assert last - first + 1 == 3
+    assert d["higher_is_better"] is True and d["dtype"] == "f64" and d["unit"] == "particle-mutation-steps/s"
+    assert abs(d["value"] - d["timed_mcmc_steps"] * d["config"]["particles_global"] / (d["ms_per_step"] * d["steps"] * 1e-3)) \
+        < 1e-6 * d["value"]
+    for key in ("roofline", "cpu_baseline", "hip_callbacks", "whole_run", "whole_run_warm", "mutation_only", "digest", "logz"):
+        assert key not in d, key
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    assert {"u.npy", "x.npy", "logl.npy", "rows.npy", "beta.npy", "logz.npy"} <= set(names)
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64 * 2 ** 20
+    u = np.load(tmp_path / "a" / "u.npy")
+    assert u.shape == (32768, 10) and np.load(tmp_path / "a" / "logl.npy").shape == (32768,)
+    assert 0.0 < float(np.load(tmp_path / "a" / "beta.npy")) <= 1.0
+    for n in names:
+        va, vb = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert va.dtype in (np.float32, np.float64), n
+        np.testing.assert_array_equal(va, vb, err_msg=n)
 
 
 def test_bench_rank_that_fails_exits_nonzero_at_once(tmp_path):

@@ -11,10 +11,10 @@ if [ "$PART" != B ]; then rm -rf "$O"; fi
 mkdir -p "$O"
 if [ "$PART" != B ]; then
 # 1. the bench line, plain
-python3 bench.py > "$O/bench_unprofiled.json" 2> "$O/bench_unprofiled.err"
+python3 bench.py --full > "$O/bench_unprofiled.json" 2> "$O/bench_unprofiled.err"
 echo "bench done"
 # 2. the same under the kernel tracer
-rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_bench" -o bench -- python3 bench.py --no-cpu-baseline > "$O/bench_under_rocprof.json" 2> "$O/bench_under_rocprof.err"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_bench" -o bench -- python3 bench.py --full --no-cpu-baseline > "$O/bench_under_rocprof.json" 2> "$O/bench_under_rocprof.err"
 echo "bench under rocprof done"
 # 3. reweight kernel: HBM traffic counters, separate passes
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$O/pmc_rw_fetch" -o f -- python3 bench.py --roofline-only > "$O/rw_fetch.json" 2> "$O/rw_fetch.err"
@@ -128,11 +128,11 @@ python3 tools/roofline_table.py --collect "$O/roof" --out "$O/roofline_table.jso
 rm -rf "$O/roof/trace" "$O/roof/fetch" "$O/roof/write"
 echo "roofline table done"
 # 8. config 4's 8-GPU shard size, un-sharded and through the sharded code path over RCCL at world size 1
-python3 bench.py --particles 131072 --no-roofline --no-cpu-baseline > "$O/bench_131k.json" 2> "$O/bench_131k.err"
-TEMPEST_AMD_FORCE_COMM=1 python3 bench.py --particles 131072 --no-roofline --no-cpu-baseline > "$O/bench_131k_comm.json" 2> "$O/bench_131k_comm.err"
+python3 bench.py --full --particles 131072 --no-roofline --no-cpu-baseline > "$O/bench_131k.json" 2> "$O/bench_131k.err"
+TEMPEST_AMD_FORCE_COMM=1 python3 bench.py --full --particles 131072 --no-roofline --no-cpu-baseline > "$O/bench_131k_comm.json" 2> "$O/bench_131k_comm.err"
 for i in 1 2 3; do
-  python3 bench.py --particles 131072 --no-roofline --no-cpu-baseline --no-hip-callbacks > "$O/ab_plain$i.json" 2>> "$O/ab.err"
-  TEMPEST_AMD_FORCE_COMM=1 python3 bench.py --particles 131072 --no-roofline --no-cpu-baseline --no-hip-callbacks > "$O/ab_comm$i.json" 2>> "$O/ab.err"
+  python3 bench.py --full --particles 131072 --no-roofline --no-cpu-baseline --no-hip-callbacks > "$O/ab_plain$i.json" 2>> "$O/ab.err"
+  TEMPEST_AMD_FORCE_COMM=1 python3 bench.py --full --particles 131072 --no-roofline --no-cpu-baseline --no-hip-callbacks > "$O/ab_comm$i.json" 2>> "$O/ab.err"
 done
 # keep the merge small: drop the raw traces that are not summarised further
 find "$O" -name "*kernel_trace.csv" -size +8M -delete

@@ -4,7 +4,7 @@
 cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 O=gpurun_out/r05/digest; rm -rf $O; mkdir -p $O
-FLAGS="--no-hip-callbacks --no-roofline --no-cpu-baseline --no-second-run --no-weak --steps 5 --warmup 2"
+FLAGS="--full --no-hip-callbacks --no-roofline --no-cpu-baseline --no-second-run --no-weak --steps 5 --warmup 2"
 timeout -k 10 300 python3 bench.py $FLAGS > $O/n1.json 2> $O/n1.err || { echo "N=1 failed"; tail -5 $O/n1.err; exit 1; }
 for N in 2 4; do
   TEMPEST_AMD_BENCH_REHEARSAL=1 timeout -k 10 400 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29600 + N)) bench.py --gpus $N $FLAGS > $O/n$N.json 2> $O/n$N.err || { echo "N=$N failed"; tail -8 $O/n$N.err; exit 1; }

@@ -25,7 +25,9 @@ callbacks are Python functions evaluated on the host (mcmc.py:152-160, core.py:3
 """
 import ctypes as C
 import hashlib
+import keyword
 import os
+import re
 import shutil
 import subprocess
 import tempfile
@@ -54,8 +56,122 @@ def _cache_dirs():
     yield Path(tempfile.gettempdir()) / "tempest_amd_plugins"
 
 
-def plugin_source(source: str) -> str:
-    return _TEMPLATE.read_text().replace("@USER_SOURCE@", source)
+# The order of the sum over observations (log_likelihood_term): chunks of SUM_LAYOUT[0] consecutive terms, blocks of SUM_LAYOUT[1]
+# consecutive chunk sums, the block sums in order.  Design constants of the template: changing them changes
+# the bits of every term-form likelihood.
+SUM_LAYOUT = (256, 64)
+
+# Which of the two evaluations of a term-form likelihood runs: the split kernel (k_user_like_split) in the first band whose
+# n_terms_min is reached, below that band's particle count; the lane-per-particle kernels elsewhere.  Both give the same bits, so
+# this table decides time only.  Measured on one MI355X with tools/bench_data_like.py: from 1000 terms on the split kernel takes
+# 0.03-0.4x the lane path's time up to 16 384 particles (0.01-0.18x at 100 000 terms), 0.5-0.77x at 65 536, and the two tie (0.88-1.0x) at
+# 262 144, where the lane path fills the machine by itself; at 100 terms the lane path wins at every size (1.0-2.8x).  Not
+# measured between 100 and 1000 terms: the lane path keeps that ground.
+DATA_LIKE_THRESHOLDS = {
+    "source": "profiles/data_like_sweep.json (tools/bench_data_like.py: cheap and dear term, n = 256 ... 1 048 576, n_terms = 1e2 ... 1e6)",
+    # (n_terms_min, split below this many particles) -- the first row whose n_terms_min <= n_terms
+    "bands": ((1_000, 262_144),),
+    # split kernel: the particle tile of a workgroup is quartered (64 -> 16 -> 4) while the grid has fewer workgroups than this
+    # (the CUs of the device the sweep ran on): 256 particles x 100 000 terms took 707 / 142 / 118 us with 64 / 16 / 4 (64 pinned in an earlier run of the tool)
+    "min_workgroups": 256,
+}
+
+_MAX_TABLES = 64
+_RESERVED = ("n_terms",)
+
+
+def prefer_split(n: int, n_terms: int) -> bool:
+    for t_min, n_below in DATA_LIKE_THRESHOLDS["bands"]:
+        if n_terms >= t_min:
+            return n < n_below
+    return False
+
+
+def _table_spec(data):
+    """Validated ((name, rank), ...) and the float64 host arrays of a `data=` mapping (insertion order)."""
+    if not isinstance(data, dict):
+        raise ValueError(f"data must be a dict of name -> array, got {type(data).__name__}")
+    if len(data) > _MAX_TABLES:
+        raise ValueError(f"data: at most {_MAX_TABLES} entries")
+    spec, arrays, members = [], {}, set(_RESERVED)
+    for name, a in data.items():
+        if not isinstance(name, str) or not re.fullmatch(r"[A-Za-z_][A-Za-z0-9_]*", name) or keyword.iskeyword(name) \
+                or name in _C_KEYWORDS:
+            raise ValueError(f"data: {name!r} is not a usable C identifier")
+        arr = _host_array(name, a)
+        mine = (name, name + "_len") if arr.ndim == 1 else (name, name + "_rows", name + "_cols")
+        clash = members.intersection(mine)
+        if clash:
+            raise ValueError(f"data: entry {name!r} collides with the generated member {sorted(clash)[0]!r} of tphu_data")
+        members.update(mine)
+        spec.append((name, arr.ndim))
+        arrays[name] = arr
+    return tuple(spec), arrays
+
+
+_C_KEYWORDS = frozenset("""auto bool break case char class const continue default delete do double else enum extern float for friend
+goto if inline int long namespace new operator private protected public register return short signed sizeof static struct switch
+template this typedef union unsigned using virtual void volatile while""".split())
+
+
+def _host_array(name, a):
+    """One data entry as a C-contiguous float64 NumPy array (1-D or 2-D, not empty)."""
+    try:
+        import torch
+        if isinstance(a, torch.Tensor):
+            if a.is_complex() or a.dtype == torch.bool:
+                raise ValueError(f"data[{name!r}]: expected real numbers, got {a.dtype}")
+            a = a.detach().to("cpu", torch.float64).numpy()
+    except ImportError:
+        pass
+    try:
+        arr = np.asarray(a)
+    except Exception as e:
+        raise ValueError(f"data[{name!r}]: not an array ({e})")
+    if arr.dtype == object or not (np.issubdtype(arr.dtype, np.floating) or np.issubdtype(arr.dtype, np.integer)):
+        raise ValueError(f"data[{name!r}]: expected real numbers, got dtype {arr.dtype}")
+    if arr.ndim not in (1, 2):
+        raise ValueError(f"data[{name!r}]: expected a 1-D or 2-D array, got {arr.ndim}-D")
+    if arr.size == 0:
+        raise ValueError(f"data[{name!r}]: empty array")
+    return np.ascontiguousarray(arr, dtype=np.float64)
+
+
+def _struct_text(tables) -> str:
+    lines = ["struct tphu_data {"]
+    for name, rank in tables:
+        lines.append(f"  const double* {name};")
+        lines.append(f"  int64_t {name}_len;" if rank == 1 else f"  int64_t {name}_rows, {name}_cols;      // row-major")
+    lines.append("  int64_t n_terms;      // terms of the sum (log_likelihood_term form), else 0")
+    lines.append("};")
+    return "\n".join(lines)
+
+
+def plugin_source(source: str, tables=None, term: bool = False) -> str:
+    """The translation unit for `source`.  tables None: callbacks of x alone (the template as it always was, byte for byte);
+    ((name, rank), ...): the callbacks take `const tphu_data& D` and every kernel and entry point carries the table;
+    term: the source gives log_likelihood_term and the library owns the sum."""
+    text = _TEMPLATE.read_text()
+    if term and tables is None:
+        tables = ()
+    keep = {"//@D": tables is not None, "//@T": term}       # lines of the data / term form only: dropped whole otherwise
+    out = []
+    for line in text.split("\n"):
+        if line[:4] in keep and line[4:5] in ("", " "):
+            if keep[line[:4]]:
+                out.append(line[5:])
+        else:
+            out.append(line)
+    text = "\n".join(out)
+    on = tables is not None
+    for mark, val in (("@D_PARAM@", ", const tphu_data D"), ("@D_REF@", ", const tphu_data& Dt"), ("@D_TARG@", ", Dt"), ("@D_ARG@", ", D"),
+                      ("@D_HOST@", ", const tphu_data* Dh"), ("@D_LAUNCH@", ", *Dh"), ("@D_KARG@", ", (void*)Dh")):
+        text = text.replace(mark, val if on else "")
+    if on:
+        text = text.replace("@DATA_STRUCT@", _struct_text(tables))
+    if term:
+        text = text.replace("@TPHU_CHUNK@", str(SUM_LAYOUT[0])).replace("@TPHU_BLOCK@", str(SUM_LAYOUT[1]))
+    return text.replace("@USER_SOURCE@", source)
 
 
 _TOOLCHAIN = None
@@ -74,9 +190,11 @@ def _toolchain_id() -> str:
     return _TOOLCHAIN
 
 
-def build_plugin(source: str, n_dim: int, verbose: bool = False) -> Path:
-    """Compile (or find in the cache) the plugin for `source`; returns the path of the shared library."""
-    text = plugin_source(source)
+def build_plugin(source: str, n_dim: int, verbose: bool = False, tables=None, term: bool = False) -> Path:
+    """Compile (or find in the cache) the plugin for `source`; returns the path of the shared library.  `tables` / `term` as in
+    plugin_source: names, ranks and the element type of the data entries are in the generated text and so in the key; values and
+    extents are not -- one compile serves every data set of that shape of table."""
+    text = plugin_source(source, tables, term)
     deps = (_CSRC / "common.h").read_bytes() + (_CSRC.parent.parent / "include" / "tempest_hip.h").read_bytes()
     key = f"|{n_dim}|{_ARCH}|{' '.join(_FLAGS)}|{_toolchain_id()}"
     tag = hashlib.sha256(text.encode() + deps + key.encode()).hexdigest()[:20]
@@ -108,13 +226,48 @@ def build_plugin(source: str, n_dim: int, verbose: bool = False) -> Path:
 class HipCallbacks:
     """prior_transform + log_likelihood as HIP device functions (see the module docstring)."""
 
+    # a source of x alone: no tables, no term form (class defaults; __init__ fills them in where `data=` / `n_terms=` are given)
+    term, tables, n_terms, data_like, split_tile, sum_layout = False, None, 0, None, 0, SUM_LAYOUT
+    _device = _dev_tables = _dstruct = _bsum = None
+
     def __init__(self, source: str, n_dim: int, fused: bool = True, verbose: bool = False, whole_step: bool = True,
-                 persistent: bool = False):
+                 persistent: bool = False, data=None, n_terms=None):
         if not isinstance(n_dim, int) or n_dim <= 0:
             raise ValueError(f"n_dim must be a positive int, got {n_dim!r}")
         for fn in ("prior_transform", "log_likelihood"):
             if fn not in source:
                 raise ValueError(f"HipCallbacks source must define __device__ {fn}(...)")
+        has_term = re.search(r"\blog_likelihood_term\s*\(", source) is not None
+        if has_term and re.search(r"\blog_likelihood\s*\(", source) is not None:
+            raise ValueError("HipCallbacks source defines both log_likelihood and log_likelihood_term: give one of them")
+        if has_term and n_terms is None:
+            raise ValueError("HipCallbacks: log_likelihood_term needs n_terms= (an int, or the name of a data entry)")
+        if n_terms is not None and not has_term:
+            raise ValueError("HipCallbacks: n_terms= goes with a source that defines log_likelihood_term")
+        self.term = has_term
+        self.tables, self._host = (None, {}) if data is None else _table_spec(data)
+        if has_term and self.tables is None:
+            self.tables = ()
+        self.n_terms = 0
+        if has_term:
+            if isinstance(n_terms, str):
+                if n_terms not in self._host:
+                    raise ValueError(f"HipCallbacks: n_terms={n_terms!r} names no data entry")
+                self._n_terms_of = n_terms
+                self.n_terms = int(self._host[n_terms].shape[0])
+            elif isinstance(n_terms, (int, np.integer)) and not isinstance(n_terms, bool) and int(n_terms) > 0:
+                self._n_terms_of = None
+                self.n_terms = int(n_terms)
+            else:
+                raise ValueError(f"HipCallbacks: n_terms must be a positive int or the name of a data entry, got {n_terms!r}")
+        self.sum_layout = SUM_LAYOUT
+        mode = os.environ.get("TEMPEST_AMD_DATA_LIKE", "").strip().lower()          # read once: lane | split pins a path
+        if mode not in ("", "lane", "split"):
+            raise ValueError(f"TEMPEST_AMD_DATA_LIKE must be 'lane' or 'split', got {mode!r}")
+        self.data_like = mode or None
+        self.split_tile = 0                    # > 0 pins the particles per workgroup of the split kernel (64, 16, 4, 1)
+        self._device = None
+        self._dev_tables, self._dstruct, self._bsum = None, None, None
         self.n_dim, self.source, self.fused = n_dim, source, bool(fused)
         self.whole_step = whole_step           # False: proposal and evaluate+accept as two kernels; "always": at any size
         # A whole run of steps in ONE cooperative launch (tphu_run) where the whole-step kernel applies.  OFF by default: measured
@@ -125,7 +278,7 @@ class HipCallbacks:
         env = os.environ.get("TEMPEST_AMD_PERSISTENT")
         self.persistent = bool(persistent) if env is None else env != "0"
         self.run_groups = 0                    # > 0 limits the workgroups of that launch (tests: several tiles per workgroup)
-        self.path = build_plugin(source, n_dim, verbose)
+        self.path = build_plugin(source, n_dim, verbose, self.tables, self.term)
         import torch  # noqa: F401  (its HIP runtime must be the one in the process, as for libtempest_hip)
         lib = C.CDLL(str(self.path))
         ptr, i64 = C.c_void_p, C.c_int64
@@ -139,11 +292,106 @@ class HipCallbacks:
                                   C.c_uint32, C.c_uint32, i64, ptr, ptr, C.c_int]
         lib.tphu_run.argtypes = [ptr, C.c_int, ptr, ptr, ptr, i64, i64, ptr, ptr, ptr, ptr, ptr, ptr, C.c_uint64, C.c_uint32, C.c_uint32,
                                  i64, ptr, ptr, ptr, ptr, C.c_double, C.c_int, C.c_int, ptr, C.c_int, C.c_int, C.c_int, C.c_int]
-        for f in (lib.tphu_prior, lib.tphu_like, lib.tphu_accept, lib.tphu_step, lib.tphu_run):
+        fns = [lib.tphu_prior, lib.tphu_like, lib.tphu_accept, lib.tphu_step, lib.tphu_run]
+        if self.tables is not None:            # a data-carrying plugin: every entry point takes the host copy of tphu_data last
+            for f in fns:
+                f.argtypes = list(f.argtypes) + [ptr]
+            fields = []
+            for name, rank in self.tables:
+                fields.append((name, ptr))
+                fields += [(name + "_len", i64)] if rank == 1 else [(name + "_rows", i64), (name + "_cols", i64)]
+            fields.append(("n_terms", i64))
+            self._struct_type = type("tphu_data", (C.Structure,), {"_fields_": fields})
+            lib.tphu_data_abi.restype = lib.tphu_data_size.restype = C.c_int
+            if lib.tphu_data_abi() != 1 or lib.tphu_data_size() != C.sizeof(self._struct_type):
+                raise TempestHipError(f"plugin {self.path}: data table layout does not match this package")
+        if self.term:
+            lib.tphu_like_split.argtypes = [ptr, ptr, i64, i64, ptr, ptr, i64, C.c_int, ptr]
+            fns.append(lib.tphu_like_split)
+        for f in fns:
             f.restype = C.c_int
         if lib.tphu_n_dim() != n_dim:
             raise TempestHipError(f"plugin {self.path} was built for n_dim={lib.tphu_n_dim()}")
         self.lib = lib
+
+    # ---------------------------------------------------------------------------------- data tables
+    @property
+    def device(self):
+        """Where host inputs and the data tables go: set by the sampler that owns this object (None: the current device)."""
+        return self._device
+
+    @device.setter
+    def device(self, dev):
+        import torch
+        self._device = None if dev is None else torch.device(dev)
+        if self._dev_tables is not None and self._device is not None and self._device.type == "cuda":
+            cur = next(iter(self._dev_tables.values()), None)
+            if cur is not None and cur.device != self._device:       # used on another device before: that copy moves
+                self._dev_tables = {k: v.to(self._device) for k, v in self._dev_tables.items()}
+                self._fill_struct()
+
+    def _fill_struct(self):
+        s = self._struct_type()
+        for name, rank in self.tables:
+            t = self._dev_tables[name]
+            setattr(s, name, t.data_ptr())
+            if rank == 1:
+                setattr(s, name + "_len", t.shape[0])
+            else:
+                setattr(s, name + "_rows", t.shape[0])
+                setattr(s, name + "_cols", t.shape[1])
+        s.n_terms = self.n_terms
+        self._dstruct = s
+
+    def _data(self):
+        """The trailing argument(s) of a data-carrying plugin's entry points (uploads the tables on first use)."""
+        if self.tables is None:
+            return ()
+        if self._dstruct is None:
+            import torch
+            dev = self._device or torch.device("cuda", torch.cuda.current_device())
+            self._dev_tables = {k: torch.from_numpy(v).to(dev) for k, v in self._host.items()}
+            self._fill_struct()
+        return (C.byref(self._dstruct),)
+
+    def update_data(self, name, array):
+        """New values for one data entry, same shape: copied into the SAME device buffer on the current stream, so a captured
+        graph (which has the pointer baked in) sees them at its next replay."""
+        if self.tables is None or name not in self._host:
+            raise ValueError(f"update_data: no data entry {name!r}")
+        arr = _host_array(name, array)
+        if arr.shape != self._host[name].shape:
+            raise ValueError(f"update_data: {name!r} has shape {self._host[name].shape}, got {arr.shape} "
+                             "(another shape needs a new HipCallbacks object)")
+        self._host[name] = arr
+        if self._dev_tables is not None:
+            import torch
+            self._dev_tables[name].copy_(torch.from_numpy(arr), non_blocking=False)
+
+    # ---------------------------------------------------------------------------- which path sums
+    def use_split(self, n) -> bool:
+        """Term-form likelihoods: True where the sum over the data is split over workgroups (k_user_like_split), False where
+        the lane that owns a particle walks it.  Same bits either way."""
+        if not self.term:
+            return False
+        if self.data_like is not None:
+            return self.data_like == "split"
+        return prefer_split(int(n), self.n_terms)
+
+    def can_fuse_accept(self, n) -> bool:
+        """Callbacks inside the Metropolis kernel (tphu_accept)?  Not where the split kernel is the faster likelihood: the step
+        then calls prior_transform / log_likelihood between tph_propose and tph_accept."""
+        return self.fused and not self.use_split(n)
+
+    def _tile(self, n, n_blocks) -> int:
+        if self.split_tile:
+            return int(self.split_tile)
+        tile = 64                               # a wave = 64 particles at one r (uniform data reads) ...
+        while tile > 1 and tile // 4 >= n:      # ... fewer particles than that: the chunks go over the lanes instead
+            tile //= 4
+        while tile > 4 and -(-n // tile) * n_blocks < DATA_LIKE_THRESHOLDS["min_workgroups"]:   # ... or too few workgroups
+            tile //= 4
+        return tile
 
     # ------------------------------------------------------------------------------------ helpers
     def _check(self, rc, what):
@@ -182,7 +430,7 @@ class HipCallbacks:
         us, was_np, one = self._soa(u)
         n = us.shape[1]
         xs = torch.empty_like(us)
-        self._check(self.lib.tphu_prior(self._stream(us), us.data_ptr(), n, n, xs.data_ptr(), n), "tphu_prior")
+        self._check(self.lib.tphu_prior(self._stream(us), us.data_ptr(), n, n, xs.data_ptr(), n, *self._data()), "tphu_prior")
         x = xs.T                                   # (n, d) strided view of the SoA buffer: no copy on the way back
         x = x[0] if one else x
         return x.cpu().numpy() if was_np else x
@@ -192,7 +440,15 @@ class HipCallbacks:
         xs, was_np, one = self._soa(x)
         n = xs.shape[1]
         ll = torch.empty(n, dtype=torch.float64, device=xs.device)
-        self._check(self.lib.tphu_like(self._stream(xs), xs.data_ptr(), n, n, ll.data_ptr()), "tphu_like")
+        if self.use_split(n):
+            span = self.sum_layout[0] * self.sum_layout[1]
+            n_blocks = -(-self.n_terms // span)
+            if self._bsum is None or self._bsum.numel() < n * n_blocks or self._bsum.device != xs.device:
+                self._bsum = torch.empty(n * n_blocks, dtype=torch.float64, device=xs.device)   # kept: no allocation per call
+            self._check(self.lib.tphu_like_split(self._stream(xs), xs.data_ptr(), n, n, ll.data_ptr(), self._bsum.data_ptr(),
+                                                 self._bsum.numel(), self._tile(n, n_blocks), *self._data()), "tphu_like_split")
+        else:
+            self._check(self.lib.tphu_like(self._stream(xs), xs.data_ptr(), n, n, ll.data_ptr(), *self._data()), "tphu_like")
         ll = ll[0] if one else ll
         return ll.cpu().numpy() if was_np else ll
 
@@ -209,7 +465,7 @@ class HipCallbacks:
         p = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
         self._check(self.lib.tphu_accept(self._stream(u), int(kernel_id), float(beta), p(u), p(x), p(logl), p(uprime),
                                          p(maha_u), p(maha_up), p(assign), n, n, int(K), p(dof), int(seed), int(tick),
-                                         int(item0), p(sums), p(ctl), p(partials), p(pending)), "tphu_accept")
+                                         int(item0), p(sums), p(ctl), p(partials), p(pending), *self._data()), "tphu_accept")
 
 
     def can_fuse_step(self, K, has_assign, n) -> bool:
@@ -218,7 +474,7 @@ class HipCallbacks:
         particles, where the step is latency-bound, but 157 -> 165 us at 1 048 576, where the proposal kernel is VALU-bound
         and the longer kernel only lowers its occupancy."""
         return (self.fused and self.whole_step and self.n_dim <= 16 and K == 1 and not has_assign
-                and (self.whole_step == "always" or n <= 512 * 1024))
+                and (self.whole_step == "always" or n <= 512 * 1024) and not self.use_split(n))
 
     def can_run(self, K, has_assign, n) -> bool:
         """A whole run of steps (the loop of mcmc.py:142-208) in ONE cooperative launch: where the whole-step kernel applies
@@ -245,7 +501,7 @@ class HipCallbacks:
         rc = self.lib.tphu_run(self._stream(u), int(kernel_id), p(u), p(logl), p(maha_u), n, n, p(modes.means_dev), p(modes.chol_dev),
                                p(winv), p(modes.dof_dev), p(sigmas), p(bc), int(seed), int(tick_propose), int(tick_accept), int(item0),
                                p(ctl), p(partials2), p(barrier), p(counts), float(n_global), int(n_steps), int(n_max), p(mailbox),
-                               int(slots), int(max_steps), int(redraw_lanes), int(self.run_groups))
+                               int(slots), int(max_steps), int(redraw_lanes), int(self.run_groups), *self._data())
         if rc == -3:
             self.persistent = False
             return False
@@ -269,7 +525,7 @@ class HipCallbacks:
         self._check(self.lib.tphu_step(self._stream(u), int(kernel_id), 0.0, p(u), p(logl), p(maha_u), n, n,
                                        p(modes.means_dev), p(modes.chol_dev), p(winv), p(modes.dof_dev), p(sigmas),
                                        p(bc), int(seed), int(tick_propose), int(tick_accept), int(item0), p(ctl), p(partials),
-                                       int(redraw_lanes)), "tphu_step")
+                                       int(redraw_lanes), *self._data()), "tphu_step")
 
 
 def fused_plugin(prior_transform, log_likelihood):

@@ -244,8 +244,8 @@ class StepEngine:
         # sharded run also exchanges the shard sums with the peers (tph_comm_p2p_*); without that exchange the ranks are combined
         # between the two launches (step(): tph_accept_sums_global)
         sums = None
-        if self.plugin is not None:       # callbacks compiled into the Metropolis kernel (hipcallbacks.py)
-            from .device import KERNEL_ID
+        if self.plugin is not None and self.plugin.can_fuse_accept(self.n):   # callbacks compiled into the Metropolis kernel
+            from .device import KERNEL_ID                                      # (hipcallbacks.py; not where its sum over data is split)
             xp = lp = None
             self.plugin.accept(KERNEL_ID[self.kernel], 0.0, self.u, None, self.logl, self.up, self.maha_u, self.maha_up,
                                self.assign, self.K, self.modes.dof_dev, self.seed, 2, self.item0, sums,
@@ -563,8 +563,8 @@ class DeviceMCMC:
                 propose()
             speculated = False
             calls += n_global
-            if self.plugin is not None:               # callbacks compiled into the Metropolis kernel (hipcallbacks.py)
-                from .device import KERNEL_ID
+            if self.plugin is not None and self.plugin.can_fuse_accept(n):   # callbacks compiled into the Metropolis kernel
+                from .device import KERNEL_ID                                 # (hipcallbacks.py; not where its sum over data is split)
                 self.plugin.accept(KERNEL_ID[self.kernel], self.beta, u, x, logl, up, maha_u, maha_up, assign, K,
                                    modes.dof_dev, self.rng.seed, self.rng.next(), self.item0, None, partials=partials)
             else:

@@ -65,6 +65,10 @@ class Sampler:
                        own loop returns its start values with nu = inf -> dof_fallback; see tempest_amd/student.py).  One GPU only.
         distributed -- shard the particles over the ranks of the initialised torch.distributed group
                        (default: yes if a group is initialised); n_particles is the GLOBAL count."""
+        if (log_likelihood_args or log_likelihood_kwargs) and \
+                type(getattr(log_likelihood, "__self__", None)).__name__ == "HipCallbacks":
+            raise ValueError("log_likelihood_args / log_likelihood_kwargs cannot reach a HipCallbacks likelihood (a device function): "
+                             "pass the arrays as HipCallbacks(source, n_dim, data={...}) and read them from the table `D`")
         wrapped = FunctionWrapper(log_likelihood, log_likelihood_args, log_likelihood_kwargs) \
             if (log_likelihood_args or log_likelihood_kwargs) else log_likelihood
         config = SamplerConfig(

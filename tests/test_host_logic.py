@@ -316,3 +316,56 @@ def test_virtual_shards_of_the_canonical_partition():
         assert n % (256 * v) == 0 and v in (48, 16, 12, 8, 6, 4, 3, 2, 1)
         assert all(n % (256 * w) != 0 for w in (48, 16, 12, 8, 6, 4, 3, 2, 1) if w > v)
     # the C side exports the same rule through the bench digest only; the kernels are pinned by tests/test_distributed.py (GPU)
+
+
+# ------------------------------------------------- the input recipes of tests/test_propose_reg_gpu.py, with the oracle alone
+@pytest.mark.parametrize("kernel", ["tpcn", "rwm"])
+@pytest.mark.parametrize("d", range(1, 17))
+def test_propose_reg_recipes_redraw_20_to_70_percent_of_first_attempts(kernel, d):
+    """The ensembles of test_propose_reg_vs_oracle_every_dimension: at every d, for one mode and for three, 20-70 % of the
+    walkers leave the cube at attempt 0 (the kernel's redraw rounds run, their list shrinks below half a wave and several lanes
+    share a walker), and fewer than 1 % run into the redraw cap (256 oracle sweeps over a handful of rows, not over hundreds)."""
+    from tests import propose_reg_cases as pc
+    for K in (1, 3):
+        e = pc.ensemble(d, kernel, K, 4097)
+        flags = pc.flags_for(d, None)
+        out0 = pc.first_attempt_out(e, flags)
+        assert 0.20 <= out0 <= 0.70, (kernel, d, K, out0)
+        capped = pc.cap_rows(e, pc.oracle(e, flags)[0]).mean()
+        assert capped < 0.01, (kernel, d, K, capped)
+
+
+@pytest.mark.parametrize("kernel", ["tpcn", "rwm"])
+@pytest.mark.parametrize("d", [1, 8, 16])
+def test_propose_reg_recipes_cap_ensembles_mix_capped_and_proposing_walkers(kernel, d):
+    """The ensembles of test_propose_reg_redraw_cap_mixed_ensemble: 10-90 % of the walkers fail all 256 attempts."""
+    from tests import propose_reg_cases as pc
+    e = pc.cap_ensemble(d, kernel)
+    capped = pc.cap_rows(e, pc.oracle(e, pc.flags_for(d, None))[0]).mean()
+    assert 0.10 <= capped <= 0.90, (kernel, d, capped)
+
+
+@pytest.mark.parametrize("d", [1, 7, 16])
+def test_propose_reg_recipes_runaway_ensemble_fails_every_attempt(d):
+    """The ensembles of test_redraw_cap_every_attempt_out_proposes_the_current_point: the oracle proposes u for every walker."""
+    from tests import propose_reg_cases as pc
+    e = pc.runaway_ensemble(d)
+    assert pc.cap_rows(e, pc.oracle(e, pc.flags_for(d, None))[0]).all()
+
+
+def test_propose_reg_launch_geometry_of_the_large_cases():
+    """tests/propose_reg_cases.py: launch_geometry restates launch_propose_reg; on a 256-CU device the large cases of
+    tests/test_propose_reg_gpu.py land where their names say."""
+    from tests import propose_reg_cases as pc
+    n_simd = 1024
+    B2, B4 = 128 * n_simd, 256 * n_simd
+    assert pc.launch_geometry(4097, n_simd) == (65, 1) and pc.launch_geometry(65536, n_simd) == (1024, 1)
+    assert pc.launch_geometry(B2 + 64 * 3 + 1, n_simd) == (2052, 1)
+    assert pc.rolled_form("tpcn", 12, B2 + 64 * 3 + 1, n_simd) and not pc.rolled_form("tpcn", 12, B2, n_simd)
+    assert not pc.rolled_form("tpcn", 11, B4, n_simd) and not pc.rolled_form("rwm", 16, B4, n_simd)
+    assert pc.launch_geometry(B4, n_simd) == (4096, 1)
+    waves, tiles = pc.launch_geometry(B4 + 4097, n_simd)          # two tiles per wave, the last wave owns one
+    assert (waves, tiles) == (2081, 2) and waves * tiles - (B4 + 4097 + 63) // 64 == 1
+    assert pc.launch_geometry(8 * B4, n_simd) == (4096, 8)
+    assert pc.launch_geometry(8 * B4 + 64 * 5 + 3, n_simd) == (4097, 8)      # ntiles > waves * REG_MAX_TILES: more waves
+    assert pc.launch_geometry(20_000, n_simd, 3) == (105, 3) and pc.launch_geometry(20_000, n_simd, 8) == (40, 8)

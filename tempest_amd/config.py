@@ -24,7 +24,7 @@ _FIELDS = (
     "pool", "clustering", "normalize", "cluster_every", "split_threshold", "n_max_clusters", "sample",
     "n_steps", "n_max_steps", "resample", "output_dir", "output_label", "random_state",
 )
-_GPU_FIELDS = ("device", "backend", "batch_prior", "graph", "student_em")
+_GPU_FIELDS = ("device", "backend", "batch_prior", "graph", "student_em", "derived")
 
 
 class SamplerConfig:
@@ -64,6 +64,7 @@ class SamplerConfig:
         batch_prior: Optional[bool] = None,
         graph: Optional[bool] = None,
         student_em: bool = False,
+        derived: Optional[Callable] = None,
     ):
         put = lambda k, v: object.__setattr__(self, k, v)  # noqa: E731
         local = locals()
@@ -149,6 +150,10 @@ class SamplerConfig:
             bad.append(f"output_label must be str or None, got {type(self.output_label)}")
         if self.graph is not None and not isinstance(self.graph, bool):
             bad.append(f"graph must be bool or None, got {self.graph!r}")
+        if self.derived is not None and not callable(self.derived):
+            bad.append(f"derived must be callable or None, got {self.derived!r}")
+        if self.derived is not None and self.blobs_dtype is not None:
+            bad.append("derived= and blobs_dtype are two sources of blobs: give one of them")
         if not isinstance(self.student_em, bool):
             bad.append(f"student_em must be bool, got {self.student_em!r}")
         if self.backend not in ("auto", "torch", "numpy"):

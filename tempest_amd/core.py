@@ -310,6 +310,8 @@ class SamplerCore:
             logw = ctx.logw(1.0, nh).cpu().numpy() - (float(m + np.log(s1)) + np.log(nh))
         comm = st.comm
         blobs = st.get_history("blobs", flat=True) if (self.config.blobs_dtype is not None and st._blobs) else None
+        # derived quantities: pure functions of x, evaluated on the rows this call returns while they are on the device
+        derive = self._derived_fn() if (return_blobs and blobs is None) else None
         if comm is None or not comm.active:
             # single shard: threshold, compaction, resampling and the gather into row-major (M, d) stay on the device;
             # only the M returned rows cross PCIe
@@ -331,8 +333,10 @@ class SamplerCore:
             else:
                 x_dev, logl_dev, w_sel = ctx.posterior_rows(sel, m_sel, w=w_dev, wdiv=wdiv)
                 weights = w_sel.cpu().numpy()
+            if derive is not None:
+                blobs = derive(x_dev)
             x, logl = x_dev.cpu().numpy(), logl_dev.cpu().numpy()
-            if blobs is not None and sel is not None:
+            if blobs is not None and derive is None and sel is not None:
                 blobs = blobs[sel.cpu().numpy()]
         else:
             # sharded run: every rank returns the posterior over the WHOLE history (rows of all shards, rank order).
@@ -351,8 +355,11 @@ class SamplerCore:
                 x_dev, logl_dev, w_sel = ctx.posterior_rows(sel, m_sel, w=w_dev, wdiv=wdiv)
                 x, logl, weights = x_dev.cpu().numpy(), logl_dev.cpu().numpy(), w_sel.cpu().numpy()
             else:
+                x_dev = torch.empty((0, st.n_dim), dtype=torch.float64, device=ctx.device)
                 x, logl, weights = np.empty((0, st.n_dim)), np.empty(0), np.empty(0)
-            if blobs is not None and sel is not None:
+            if derive is not None:               # this rank's kept rows (none: an empty (0, k) block), gathered like x below
+                blobs = derive(x_dev)
+            elif blobs is not None and sel is not None:
                 blobs = blobs[sel.cpu().numpy()]
             x, logl, weights = comm.gather_rows(x), comm.gather_rows(logl), comm.gather_rows(weights)
             if blobs is not None:
@@ -370,10 +377,53 @@ class SamplerCore:
                 weights = np.ones(len(idx)) / len(idx)
         out = [x, weights, logl]
         if return_blobs and blobs is not None:
+            if derive is not None and blobs.ndim == 2 and blobs.shape[1] == 1:
+                blobs = blobs[:, 0]              # one value per sample: (M,), the rule of _pack_blobs
             out.append(blobs)
         if return_logw:
             out.append(logw)
         return tuple(out)
+
+    def _derived_fn(self):
+        """rows (M, d) on the device -> the derived quantities as a host (M, k) float64 array, or None without a derived function:
+        config.derived, else the `derived` of the HipCallbacks object the likelihood belongs to."""
+        import torch
+        from .hipcallbacks import HipCallbacks
+        fn = self.config.derived
+        owner = getattr(self.config.log_likelihood, "__self__", None)
+        if fn is None and isinstance(owner, HipCallbacks) and owner.n_derived > 0:
+            fn = owner.derived
+        if fn is None:
+            return None
+        on_device = isinstance(getattr(fn, "__self__", None), HipCallbacks)
+        width = fn.__self__.n_derived if on_device else None      # a plugin's width is known without a call
+        if on_device:
+            if fn.__self__.device is None:
+                fn.__self__.device = self.state.device
+        elif self.config.backend == "auto":
+            self._ensure_callbacks()
+            if self.callbacks.backend is None:
+                self.callbacks._probe()
+            on_device = self.callbacks.backend == "torch"
+        else:
+            on_device = self.config.backend == "torch"
+
+        def run(x_dev):
+            m = x_dev.shape[0]
+            if m == 0 and width is not None:     # a rank with no kept rows: an empty (0, k) block, nothing launched
+                return np.empty((0, width), dtype=np.float64)
+            # (a user's callable gets the (0, d) array itself -- no made-up row that might lie outside its domain -- and must
+            # answer with (0, k), as every vectorised NumPy / torch expression does)
+            b = fn(x_dev) if on_device else fn(x_dev.cpu().numpy())
+            if isinstance(b, torch.Tensor):
+                b = b.detach().to("cpu", torch.float64).numpy()
+            b = np.ascontiguousarray(b, dtype=np.float64)
+            if b.ndim == 1:
+                b = b.reshape(m, 1)
+            if b.ndim != 2 or b.shape[0] != m:
+                raise ValueError(f"derived: expected ({m}, k) values for ({m}, {x_dev.shape[1]}) points, got shape {b.shape}")
+            return b
+        return run
 
     def compute_evidence(self):
         return self.state.get_current("logz"), getattr(self, "logz_err", None)

@@ -77,6 +77,12 @@ DATA_LIKE_THRESHOLDS = {
 }
 
 _MAX_TABLES = 64
+# derived(x, out): the N_DERIVED values of a row are registers of the lane that owns it, beside the row's N_DIM
+MAX_DERIVED = 32
+# rows per workgroup of the row-major derived kernel (k_user_derived): the largest whose two LDS images -- rows x (n_dim | 1) and
+# rows x (n_derived | 1) doubles -- fit DERIVED_LDS_BYTES; none fits: the direct (lane per row) kernel.  The template's rule, restated.
+DERIVED_TILES = (256, 128, 64)
+DERIVED_LDS_BYTES = 65536
 _RESERVED = ("n_terms",)
 
 
@@ -85,6 +91,30 @@ def prefer_split(n: int, n_terms: int) -> bool:
         if n_terms >= t_min:
             return n < n_below
     return False
+
+
+def derived_tiles(n_dim: int, n_derived: int):
+    """The LDS tiles (rows per workgroup) the row-major derived kernel can take at this shape, largest first; () where it falls
+    back to the direct kernel."""
+    return tuple(r for r in DERIVED_TILES if r * ((n_dim | 1) + (n_derived | 1)) * 8 <= DERIVED_LDS_BYTES)
+
+
+def _has_derived(source: str) -> bool:
+    """The source DEFINES derived (`void derived(`): the word alone, in a comment or a name, is not a definition."""
+    return re.search(r"\bvoid\s+derived\s*\(", source) is not None
+
+
+def _check_n_derived(source, n_derived) -> int:
+    has = _has_derived(source)
+    if n_derived is None:
+        if has:
+            raise ValueError("HipCallbacks: the source defines derived(...): give n_derived= (how many values it writes)")
+        return 0
+    if not has:
+        raise ValueError("HipCallbacks: n_derived= goes with a source that defines __device__ void derived(const double* x, double* out)")
+    if isinstance(n_derived, bool) or not isinstance(n_derived, (int, np.integer)) or not 0 < int(n_derived) <= MAX_DERIVED:
+        raise ValueError(f"HipCallbacks: n_derived must be a positive int, at most {MAX_DERIVED}, got {n_derived!r}")
+    return int(n_derived)
 
 
 def _table_spec(data):
@@ -147,14 +177,16 @@ def _struct_text(tables) -> str:
     return "\n".join(lines)
 
 
-def plugin_source(source: str, tables=None, term: bool = False) -> str:
+def plugin_source(source: str, tables=None, term: bool = False, *, derived: bool = False) -> str:
     """The translation unit for `source`.  tables None: callbacks of x alone (the template as it always was, byte for byte);
     ((name, rank), ...): the callbacks take `const tphu_data& D` and every kernel and entry point carries the table;
-    term: the source gives log_likelihood_term and the library owns the sum."""
+    term: the source gives log_likelihood_term and the library owns the sum; derived: the source gives derived(x, out) and the
+    plugin gets k_user_derived / tphu_derived (compiled with -DN_DERIVED=k)."""
     text = _TEMPLATE.read_text()
     if term and tables is None:
         tables = ()
-    keep = {"//@D": tables is not None, "//@T": term}       # lines of the data / term form only: dropped whole otherwise
+    # lines of the data / term form / a source with derived() only: dropped whole otherwise
+    keep = {"//@D": tables is not None, "//@T": term, "//@X": derived}
     out = []
     for line in text.split("\n"):
         if line[:4] in keep and line[4:5] in ("", " "):
@@ -165,7 +197,8 @@ def plugin_source(source: str, tables=None, term: bool = False) -> str:
     text = "\n".join(out)
     on = tables is not None
     for mark, val in (("@D_PARAM@", ", const tphu_data D"), ("@D_REF@", ", const tphu_data& Dt"), ("@D_TARG@", ", Dt"), ("@D_ARG@", ", D"),
-                      ("@D_HOST@", ", const tphu_data* Dh"), ("@D_LAUNCH@", ", *Dh"), ("@D_KARG@", ", (void*)Dh")):
+                      ("@D_HOST@", ", const tphu_data* Dh"), ("@D_LAUNCH@", ", *Dh"), ("@D_KARG@", ", (void*)Dh"),
+                      ("@D_NONNULL@", " && Dh")):
         text = text.replace(mark, val if on else "")
     if on:
         text = text.replace("@DATA_STRUCT@", _struct_text(tables))
@@ -190,13 +223,15 @@ def _toolchain_id() -> str:
     return _TOOLCHAIN
 
 
-def build_plugin(source: str, n_dim: int, verbose: bool = False, tables=None, term: bool = False) -> Path:
+def build_plugin(source: str, n_dim: int, verbose: bool = False, tables=None, term: bool = False, *, n_derived: int = 0) -> Path:
     """Compile (or find in the cache) the plugin for `source`; returns the path of the shared library.  `tables` / `term` as in
     plugin_source: names, ranks and the element type of the data entries are in the generated text and so in the key; values and
-    extents are not -- one compile serves every data set of that shape of table."""
-    text = plugin_source(source, tables, term)
+    extents are not -- one compile serves every data set of that shape of table.  n_derived > 0: the source has derived(); only then
+    do -DN_DERIVED and its part of the key exist, so every other source keeps the file name it had."""
+    text = plugin_source(source, tables, term, derived=n_derived > 0)
+    defs = [f"-DN_DIM={int(n_dim)}"] + ([f"-DN_DERIVED={int(n_derived)}"] if n_derived > 0 else [])
     deps = (_CSRC / "common.h").read_bytes() + (_CSRC.parent.parent / "include" / "tempest_hip.h").read_bytes()
-    key = f"|{n_dim}|{_ARCH}|{' '.join(_FLAGS)}|{_toolchain_id()}"
+    key = f"|{n_dim}|{_ARCH}|{' '.join(_FLAGS)}|{_toolchain_id()}" + (f"|derived={int(n_derived)}" if n_derived > 0 else "")
     tag = hashlib.sha256(text.encode() + deps + key.encode()).hexdigest()[:20]
     name = f"tphu_{n_dim}d_{tag}.so"
     for d in _cache_dirs():
@@ -210,7 +245,7 @@ def build_plugin(source: str, n_dim: int, verbose: bool = False, tables=None, te
                 src = Path(tmp) / "plugin.hip"
                 src.write_text(text)
                 out = Path(tmp) / name
-                cmd = [_hipcc(), *_FLAGS, f"-DN_DIM={int(n_dim)}", f"-I{_CSRC}", str(src), "-o", str(out)]
+                cmd = [_hipcc(), *_FLAGS, *defs, f"-I{_CSRC}", str(src), "-o", str(out)]
                 if verbose:
                     print(" ".join(cmd))
                 r = subprocess.run(cmd, capture_output=True, text=True)
@@ -228,10 +263,11 @@ class HipCallbacks:
 
     # a source of x alone: no tables, no term form (class defaults; __init__ fills them in where `data=` / `n_terms=` are given)
     term, tables, n_terms, data_like, split_tile, sum_layout = False, None, 0, None, 0, SUM_LAYOUT
+    n_derived, derived_tile = 0, 0
     _device = _dev_tables = _dstruct = _bsum = None
 
     def __init__(self, source: str, n_dim: int, fused: bool = True, verbose: bool = False, whole_step: bool = True,
-                 persistent: bool = False, data=None, n_terms=None):
+                 persistent: bool = False, data=None, n_terms=None, n_derived=None):
         if not isinstance(n_dim, int) or n_dim <= 0:
             raise ValueError(f"n_dim must be a positive int, got {n_dim!r}")
         for fn in ("prior_transform", "log_likelihood"):
@@ -244,6 +280,8 @@ class HipCallbacks:
             raise ValueError("HipCallbacks: log_likelihood_term needs n_terms= (an int, or the name of a data entry)")
         if n_terms is not None and not has_term:
             raise ValueError("HipCallbacks: n_terms= goes with a source that defines log_likelihood_term")
+        self.n_derived = _check_n_derived(source, n_derived)
+        self.derived_tile = 0                  # > 0 pins the row-major derived kernel: 256 / 128 / 64 rows per workgroup, 1 = direct
         self.term = has_term
         self.tables, self._host = (None, {}) if data is None else _table_spec(data)
         if has_term and self.tables is None:
@@ -278,7 +316,7 @@ class HipCallbacks:
         env = os.environ.get("TEMPEST_AMD_PERSISTENT")
         self.persistent = bool(persistent) if env is None else env != "0"
         self.run_groups = 0                    # > 0 limits the workgroups of that launch (tests: several tiles per workgroup)
-        self.path = build_plugin(source, n_dim, verbose, self.tables, self.term)
+        self.path = build_plugin(source, n_dim, verbose, self.tables, self.term, n_derived=self.n_derived)
         import torch  # noqa: F401  (its HIP runtime must be the one in the process, as for libtempest_hip)
         lib = C.CDLL(str(self.path))
         ptr, i64 = C.c_void_p, C.c_int64
@@ -293,6 +331,10 @@ class HipCallbacks:
         lib.tphu_run.argtypes = [ptr, C.c_int, ptr, ptr, ptr, i64, i64, ptr, ptr, ptr, ptr, ptr, ptr, C.c_uint64, C.c_uint32, C.c_uint32,
                                  i64, ptr, ptr, ptr, ptr, C.c_double, C.c_int, C.c_int, ptr, C.c_int, C.c_int, C.c_int, C.c_int]
         fns = [lib.tphu_prior, lib.tphu_like, lib.tphu_accept, lib.tphu_step, lib.tphu_run]
+        if self.n_derived:
+            lib.tphu_derived.argtypes = [ptr, ptr, i64, i64, ptr, i64, C.c_int, C.c_int]
+            fns.append(lib.tphu_derived)
+            lib.tphu_n_derived.restype = lib.tphu_derived_rows.restype = C.c_int
         if self.tables is not None:            # a data-carrying plugin: every entry point takes the host copy of tphu_data last
             for f in fns:
                 f.argtypes = list(f.argtypes) + [ptr]
@@ -312,6 +354,9 @@ class HipCallbacks:
             f.restype = C.c_int
         if lib.tphu_n_dim() != n_dim:
             raise TempestHipError(f"plugin {self.path} was built for n_dim={lib.tphu_n_dim()}")
+        if self.n_derived and (lib.tphu_n_derived() != self.n_derived
+                               or lib.tphu_derived_rows() != (derived_tiles(n_dim, self.n_derived) or (0,))[0]):
+            raise TempestHipError(f"plugin {self.path}: derived() shape or tile rule does not match this package")
         self.lib = lib
 
     # ---------------------------------------------------------------------------------- data tables
@@ -451,6 +496,52 @@ class HipCallbacks:
             self._check(self.lib.tphu_like(self._stream(xs), xs.data_ptr(), n, n, ll.data_ptr(), *self._data()), "tphu_like")
         ll = ll[0] if one else ll
         return ll.cpu().numpy() if was_np else ll
+
+    def _on_table_device(self, t):
+        """The data tables are pointers into ONE device's memory: rows on another device must not meet them in a kernel."""
+        if self.tables:
+            self._data()
+            tab = next(iter(self._dev_tables.values()))
+            if tab.device != t.device:
+                raise ValueError(f"HipCallbacks.derived: the points are on {t.device}, the data tables on {tab.device}")
+
+    def derived(self, x):
+        """(n, n_dim) points [or one point] -> (n, n_derived) values of the source's derived() [or (n_derived,)], same container
+        kind as the input.  Contiguous rows go through the row-major kernel as they are (what posterior() hands over); any other
+        view is read dimension-major, like the other callbacks.  Same bits either way."""
+        import torch
+        if not self.n_derived:
+            raise TempestHipError("HipCallbacks.derived: the source defines no derived(...) (give it and n_derived=)")
+        k = self.n_derived
+        rows = isinstance(x, torch.Tensor) and x.dim() == 2 and x.is_cuda and x.dtype == torch.float64 and x.is_contiguous()
+        if not isinstance(x, torch.Tensor):
+            xa = np.asarray(x, dtype=np.float64)
+            rows = xa.ndim in (1, 2) and xa.shape[-1] == self.n_dim
+        if rows:
+            was_np, one = not isinstance(x, torch.Tensor), False
+            if was_np:
+                one = xa.ndim == 1
+                x = torch.from_numpy(np.ascontiguousarray(xa.reshape(-1, self.n_dim))).to(
+                    self._device or torch.device("cuda", torch.cuda.current_device()))
+            if x.shape[1] != self.n_dim:
+                raise ValueError(f"expected (..., {self.n_dim}) points, got {tuple(x.shape)}")
+            n = x.shape[0]
+            out = torch.empty((n, k), dtype=torch.float64, device=x.device)
+            if n:
+                self._on_table_device(x)
+                self._check(self.lib.tphu_derived(self._stream(x), x.data_ptr(), n, self.n_dim, out.data_ptr(), k, 1,
+                                                  int(self.derived_tile), *self._data()), "tphu_derived")
+        else:
+            xs, was_np, one = self._soa(x)
+            n = xs.shape[1]
+            outs = torch.empty((k, n), dtype=torch.float64, device=xs.device)
+            if n:
+                self._on_table_device(xs)
+                self._check(self.lib.tphu_derived(self._stream(xs), xs.data_ptr(), n, n, outs.data_ptr(), n, 0, 0, *self._data()),
+                            "tphu_derived")
+            out = outs.T
+        out = out[0] if one else out
+        return out.cpu().numpy() if was_np else out
 
     # ------------------------------------------------------------------------------ fused MCMC step
     def accept(self, kernel_id, beta, u, x, logl, uprime, maha_u, maha_up, assign, K, dof, seed, tick, item0, sums,

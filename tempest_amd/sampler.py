@@ -47,6 +47,7 @@ class Sampler:
         graph: Optional[bool] = None,
         distributed: Optional[bool] = None,
         student_em: bool = False,
+        derived: Optional[callable] = None,
     ):
         """GPU additions (keyword-only):
         device      -- GPU index (default: current torch device; LOCAL_RANK under torchrun).
@@ -63,6 +64,12 @@ class Sampler:
         student_em  -- True: every proposal mode's (mu, Sigma, nu) comes from the Student-t EM of tempest/student.py:66-116 with a
                        working degrees-of-freedom update, started from the default estimator (an EXTENSION: the reference's
                        own loop returns its start values with nu = inf -> dof_fallback; see tempest_amd/student.py).  One GPU only.
+        derived     -- vectorised callable (n, n_dim) -> (n, k) [or (n,)]: derived quantities that are pure functions of x (and of
+                       the data the callable holds).  Evaluated only by posterior(return_blobs=True), on the returned rows, and
+                       handed back as the blobs (float64).  It gets a torch tensor under backend="torch", a NumPy array otherwise.
+                       None (default): the `derived` of the HipCallbacks object `log_likelihood` belongs to, if its source has one.
+                       Not state: never written into a checkpoint.  On a sharded run a rank that keeps no rows calls it with
+                       a (0, n_dim) array and expects (0, k) back.
         distributed -- shard the particles over the ranks of the initialised torch.distributed group
                        (default: yes if a group is initialised); n_particles is the GLOBAL count."""
         if (log_likelihood_args or log_likelihood_kwargs) and \
@@ -79,7 +86,7 @@ class Sampler:
             cluster_every=cluster_every, split_threshold=split_threshold, n_max_clusters=n_max_clusters,
             sample=sample, n_steps=n_steps, n_max_steps=n_max_steps, resample=resample, output_dir=output_dir,
             output_label=output_label, random_state=random_state, device=device, backend=backend,
-            batch_prior=batch_prior, graph=graph, student_em=student_em)
+            batch_prior=batch_prior, graph=graph, student_em=student_em, derived=derived)
         comm = None
         if distributed is not False:
             from .comm import Comm
@@ -122,7 +129,9 @@ class Sampler:
 
     def posterior(self, resample: bool = False, return_blobs: bool = False, trim_importance_weights: bool = True,
                   return_logw: bool = False, ess_trim: float = 0.99, bins_trim: int = 1000) -> tuple:
-        """(x, weights, logl[, blobs][, logw]) over the whole history, NumPy, C-contiguous, copies."""
+        """(x, weights, logl[, blobs][, logw]) over the whole history, NumPy, C-contiguous, copies.  The blobs are the host
+        likelihood's (blobs_dtype), or the derived quantities of the returned rows (`derived=`, or a HipCallbacks source with
+        derived()): evaluated here, on the device, from x.  Without either there is no blobs entry."""
         return self._core.compute_posterior(resample=resample, return_blobs=return_blobs,
                                             trim_importance_weights=trim_importance_weights, return_logw=return_logw,
                                             ess_trim=ess_trim, bins_trim=bins_trim)

@@ -1,0 +1,529 @@
+"""HipCallbacks derived quantities (tempest_amd/hipcallbacks.py): `derived(x, out)` in the user's source,
+evaluated on the device on the rows posterior(return_blobs=True) returns.
+
+CPU: sources without derived() generate the text and the file name they always did, plugins with it compile for gfx950 in every
+form and export tphu_derived, every validation error.  GPU: cb.derived against a NumPy restatement to the bit, row-major ==
+dimension-major == every tile, guard cells, two streams, whole runs (one GPU, two ranks), checkpoints, Sampler(derived=torch_fn)."""
+import ctypes
+import hashlib
+import json
+import os
+import shutil
+import socket
+
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+
+needs_hipcc = pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"),
+                                 reason="hipcc not available")
+
+# tests/test_hipcallbacks.py's SRC (any even N_DIM)
+BASE = '''
+__device__ void prior_transform(const double* u, double* x) {
+#pragma unroll
+  for (int j = 0; j < N_DIM; ++j) x[j] = 20.0 * u[j] - 10.0;
+}
+__device__ double log_likelihood(const double* x) {
+  double s = 0.0;
+#pragma unroll
+  for (int j = 0; j < N_DIM; j += 2) {
+    double a = x[j] * x[j] - x[j + 1], b = x[j] - 1.0;
+    s += 10.0 * a * a + b * b;
+  }
+  return -s;
+}
+'''
+# any N_DIM (the shapes of the kernel test: 3 is odd)
+BASE_ANY = '''
+__device__ void prior_transform(const double* u, double* x) {
+  for (int j = 0; j < N_DIM; ++j) x[j] = 20.0 * u[j] - 10.0;
+}
+__device__ double log_likelihood(const double* x) {
+  double s = 0.0;
+  for (int j = 0; j < N_DIM; ++j) s += x[j] * x[j];
+  return -0.5 * s;
+}
+'''
+# one rounding per value, nothing a contraction could fuse: a sum, a product, a difference, a quotient (|x| <= 5: the divisor >= 2)
+ARITH = '''
+__device__ void derived(const double* x, double* out) {
+  for (int m = 0; m < N_DERIVED; ++m) {
+    const double a = x[m % N_DIM], b = x[(m + 1) % N_DIM];
+    const double den = b + 7.0;
+    out[m] = m % 4 == 0 ? a + b : m % 4 == 1 ? a * b : m % 4 == 2 ? a - b : a / den;
+  }
+}
+'''
+EXPLOG = '''
+__device__ void derived(const double* x, double* out) {
+  const double q = x[1] * x[1];
+  out[0] = exp(0.1 * x[0]) + log(q + 1.0);
+  out[1] = log(exp(0.3 * x[N_DIM - 1]) + 2.0);
+}
+'''
+PRIOR_D = '''
+__device__ void prior_transform(const double* u, double* x, const tphu_data& D) {
+  for (int j = 0; j < N_DIM; ++j) x[j] = 10.0 * u[j] - 5.0;
+}
+'''
+# a table lookup from D: row m of the 2-D entry, indexed through its extents
+DERIVED_D = '''
+__device__ void derived(const double* x, double* out, const tphu_data& D) {
+  for (int m = 0; m < N_DERIVED; ++m) {
+    const double t = D.tab[(m % D.tab_rows) * D.tab_cols + 1];
+    out[m] = m % 2 == 0 ? x[m % N_DIM] + t : x[m % N_DIM] * t;
+  }
+}
+'''
+WHOLE_D = PRIOR_D + '''
+__device__ double log_likelihood(const double* x, const tphu_data& D) {
+  double s = 0.0;
+  for (int64_t r = 0; r < D.tab_rows; ++r) { const double z = x[0] - D.tab[r * D.tab_cols]; s += -0.5 * z * z; }
+  return s;
+}
+'''
+TERM_D = PRIOR_D + '''
+__device__ double log_likelihood_term(const double* x, int64_t r, const tphu_data& D) {
+  const double z = x[0] - D.tab[r * D.tab_cols];
+  return -0.5 * z * z;
+}
+'''
+TAB = np.random.RandomState(5).uniform(-2.0, 2.0, size=(7, 3))
+
+SIZES = (1, 63, 64, 65, 700, 3001, (1 << 20) + 3)
+
+
+def f_arith(x, k):
+    """ARITH, column by column, operation by operation."""
+    d = x.shape[1]
+    out = np.empty((len(x), k))
+    for m in range(k):
+        a, b = x[:, m % d], x[:, (m + 1) % d]
+        out[:, m] = (a + b, a * b, a - b, a / (b + 7.0))[m % 4]
+    return out
+
+
+def f_arith_torch(x, k):
+    d = x.shape[1]
+    cols = []
+    for m in range(k):
+        a, b = x[:, m % d], x[:, (m + 1) % d]
+        cols.append((a + b, a * b, a - b, a / (b + 7.0))[m % 4])
+    return torch.stack(cols, dim=1)
+
+
+def f_table(x, k):
+    d = x.shape[1]
+    out = np.empty((len(x), k))
+    for m in range(k):
+        t = TAB[m % len(TAB), 1]
+        out[:, m] = x[:, m % d] + t if m % 2 == 0 else x[:, m % d] * t
+    return out
+
+
+def points(n, d, seed=1):
+    return np.random.RandomState(seed).uniform(-5.0, 5.0, size=(n, d))
+
+
+def need_gpu():
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+
+
+# ------------------------------------------------------------------------------------------------- CPU
+# What the parent of this feature (e14e8c5) generated for the sources of tests/test_hipcallbacks_data.py: SHA-256 of the text, and
+# the file name build_plugin gave it.  The name also hashes csrc/common.h, include/tempest_hip.h and `hipcc --version`: the recorded
+# names hold where those are the recorded ones (PARENT_ENV); everywhere the name must be what the parent's formula gives.
+PARENT_ENV = "2b62480092b80b7ec47b1333ab23a4d077792b10d3b49d36aad7954ec603477e"
+REG_TABLES = (("t", 1), ("y", 1), ("s", 1), ("c", 1))
+
+
+def parent_cases():
+    from tests import test_hipcallbacks_data as T
+    return (
+        (T.OLD_SRC, 10, None, False, "85422a8c6c6b7f15300384fe0cff150dc7d93d0c9030862000df9219ef6bc467", "tphu_10d_31906f1f808b4d3dacbe.so"),
+        (T.OLD_SRC, 3, None, False, "85422a8c6c6b7f15300384fe0cff150dc7d93d0c9030862000df9219ef6bc467", "tphu_3d_b79b99c51b8a123cb756.so"),
+        (T.REG, 3, REG_TABLES, True, "2f76975f583edfd024e56ecb6d3fc91bdb72f594fe1beac0713e94a88e10c03d", "tphu_3d_8cf3797ac7a56213842b.so"),
+        (T.WHOLE, 3, (("obs", 2),), False, "2852dc283614e005b4c163dd6beed48e08e3f5a267d889d59fb34ebfe45335a1", "tphu_3d_04a943dee0844861b2bf.so"),
+    )
+
+
+def test_sources_without_derived_generate_the_parent_text():
+    from tempest_amd.hipcallbacks import plugin_source
+    for src, _, tables, term, sha, _ in parent_cases():
+        text = plugin_source(src, tables, term)
+        assert hashlib.sha256(text.encode()).hexdigest() == sha
+        assert text == plugin_source(src, tables, term, derived=False)
+        assert "derived" not in text and "N_DERIVED" not in text and "//@X" not in text
+    with_x = plugin_source(BASE + ARITH, derived=True)
+    assert "k_user_derived" in with_x and "tphu_derived(" in with_x and "//@X" not in with_x
+    assert "@" not in with_x.replace(BASE + ARITH, "")
+
+
+@needs_hipcc
+def test_sources_without_derived_keep_their_file_name():
+    from tempest_amd import hipcallbacks as H
+    deps = (H._CSRC / "common.h").read_bytes() + (H._CSRC.parent.parent / "include" / "tempest_hip.h").read_bytes()
+    recorded_env = hashlib.sha256(deps + H._toolchain_id().encode()).hexdigest() == PARENT_ENV
+    for src, n_dim, tables, term, sha, name in parent_cases():
+        got = H.build_plugin(src, n_dim, tables=tables, term=term).name
+        # the parent's formula, restated: text + the two headers + "|n_dim|arch|flags|toolchain"
+        text = H.plugin_source(src, tables, term)
+        key = f"|{n_dim}|gfx950|-O3 -std=c++17 -fPIC -shared --offload-arch=gfx950 -ffp-contract=on -Wno-unused-function|{H._toolchain_id()}"
+        assert got == f"tphu_{n_dim}d_{hashlib.sha256(text.encode() + deps + key.encode()).hexdigest()[:20]}.so"
+        if recorded_env:
+            assert got == name
+    a = H.build_plugin(BASE + ARITH, 4, n_derived=2)
+    assert a != H.build_plugin(BASE + ARITH, 4, n_derived=3)                  # N_DERIVED is in the key
+
+
+@needs_hipcc
+def test_derived_plugins_build_and_export_the_entry_point():
+    from tempest_amd.hipcallbacks import build_plugin
+    tabs = (("tab", 2),)
+    built = (build_plugin(BASE + ARITH, 4, n_derived=2),
+             build_plugin(WHOLE_D + DERIVED_D, 3, tables=tabs, n_derived=2),
+             build_plugin(TERM_D + DERIVED_D, 3, tables=tabs, term=True, n_derived=2))
+    for path in built:
+        lib = ctypes.CDLL(str(path))
+        for sym in ("tphu_derived", "tphu_n_derived", "tphu_derived_rows", "tphu_prior", "tphu_like", "tphu_accept", "tphu_step", "tphu_run"):
+            assert hasattr(lib, sym), sym
+        assert lib.tphu_n_derived() == 2 and lib.tphu_derived_rows() == 256 and lib.tphu_abi() == 3
+    assert hasattr(ctypes.CDLL(str(built[2])), "tphu_like_split")
+    plain = ctypes.CDLL(str(build_plugin(BASE, 4)))
+    assert not hasattr(plain, "tphu_derived") and not hasattr(plain, "tphu_n_derived") and plain.tphu_abi() == 3
+
+
+def test_tile_rule():
+    """Rows per workgroup: the largest of 256 / 128 / 64 whose LDS images (odd pitches) fit 64 KiB; none: the direct kernel."""
+    from tempest_amd.hipcallbacks import MAX_DERIVED, derived_tiles
+    assert derived_tiles(3, 1) == derived_tiles(10, 2) == (256, 128, 64)
+    assert derived_tiles(10, MAX_DERIVED) == (128, 64)
+    assert derived_tiles(40, 2) == (128, 64)
+    assert derived_tiles(112, 2) == (64,)                  # the widest shape the library's own kernels are tested at
+    assert derived_tiles(130, 1) == ()
+    for d in range(1, 200):
+        for k in (1, 2, MAX_DERIVED):
+            for r in derived_tiles(d, k):
+                assert r * ((d | 1) + (k | 1)) * 8 <= 65536
+
+
+@pytest.mark.parametrize("source,kw,match", [
+    (BASE + ARITH, {}, "give n_derived="),
+    (BASE, {"n_derived": 2}, "goes with a source that defines"),
+    (BASE + ARITH, {"n_derived": True}, "positive int"),
+    (BASE + ARITH, {"n_derived": 0}, "positive int"),
+    (BASE + ARITH, {"n_derived": -1}, "positive int"),
+    (BASE + ARITH, {"n_derived": 2.0}, "positive int"),
+    (BASE + ARITH, {"n_derived": 33}, "at most 32"),
+])
+def test_derived_validation_raises_before_the_compiler_runs(source, kw, match, monkeypatch):
+    import tempest_amd as tp
+    from tempest_amd import hipcallbacks
+    assert hipcallbacks.MAX_DERIVED == 32
+    monkeypatch.setattr(hipcallbacks, "build_plugin", lambda *a, **k: pytest.fail("the compiler ran"))
+    with pytest.raises(ValueError, match=match):
+        tp.HipCallbacks(source, 4, **kw)
+
+
+def test_the_word_derived_in_a_comment_is_not_a_definition(monkeypatch):
+    import tempest_amd as tp
+    from tempest_amd import hipcallbacks
+    assert not hipcallbacks._has_derived(BASE + "// the rate is derived (see eq. 3) from x\n")
+    assert hipcallbacks._has_derived(BASE + ARITH)
+    monkeypatch.setattr(hipcallbacks, "build_plugin", lambda *a, **k: pytest.fail("the compiler ran"))
+    with pytest.raises(ValueError, match="goes with a source that defines"):
+        tp.HipCallbacks(BASE + "// derived (see eq. 3)\n", 4, n_derived=1)
+
+
+def test_sampler_refuses_two_sources_of_blobs():
+    import tempest_amd as tp
+    pt, ll = (lambda u: u), (lambda x: 0.0)
+    with pytest.raises(ValueError, match="two sources of blobs"):
+        tp.Sampler(pt, ll, 2, blobs_dtype="float64", derived=lambda x: x)
+    with pytest.raises(ValueError, match="derived must be callable"):
+        tp.Sampler(pt, ll, 2, derived=3)
+    with pytest.raises(ValueError, match="Cannot vectorize likelihood with blobs"):
+        tp.Sampler(pt, ll, 2, vectorize=True, blobs_dtype="float64")
+    from tempest_amd.config import _GPU_FIELDS
+    assert "derived" in _GPU_FIELDS
+
+
+# ------------------------------------------------------------------------------------------------- GPU
+def all_layouts(cb, xt):
+    """cb.derived of the same rows: contiguous row-major at the plugin's own tile, at every tile it can take (1 = direct), and as the
+    dimension-major view; equal bits asserted, the first returned."""
+    from tempest_amd.hipcallbacks import derived_tiles
+    assert xt.is_contiguous()
+    cb.derived_tile = 0
+    first = cb.derived(xt)
+    assert first.shape == (xt.shape[0], cb.n_derived) and first.is_contiguous()
+    for tile in derived_tiles(cb.n_dim, cb.n_derived) + (1,):
+        cb.derived_tile = tile
+        assert torch.equal(cb.derived(xt), first), f"tile {tile}"
+    cb.derived_tile = 0
+    view = xt.T.contiguous().T                                 # (n, d) strided view of a (d, n) buffer
+    assert not view.is_contiguous() or xt.shape[0] == 1 or xt.shape[1] == 1
+    soa = cb.derived(view)
+    assert soa.shape == first.shape and torch.equal(soa, first)
+    return first
+
+
+@pytest.mark.gpu
+@needs_hipcc
+@pytest.mark.parametrize("n_dim,n_derived", [(3, 1), (3, 2), (10, 2), (10, 32), (40, 2), (130, 1)])
+def test_derived_matches_numpy_bit_for_bit(n_dim, n_derived):
+    """(10, 32): n_derived at its limit, 128 rows per workgroup; (40, 2): 128 rows; (130, 1): no tile fits, the direct kernel."""
+    import tempest_amd as tp
+    need_gpu()
+    cb = tp.HipCallbacks(BASE_ANY + ARITH, n_dim, n_derived=n_derived)
+    assert cb.n_derived == n_derived
+    for n in SIZES:
+        x = points(n, n_dim, seed=n)
+        got = all_layouts(cb, torch.from_numpy(x).cuda())
+        np.testing.assert_array_equal(got.cpu().numpy(), f_arith(x, n_derived), err_msg=f"n={n}")
+    x = points(700, n_dim)
+    out = cb.derived(x)                                        # NumPy in -> NumPy out
+    assert isinstance(out, np.ndarray) and out.shape == (700, n_derived)
+    np.testing.assert_array_equal(out, f_arith(x, n_derived))
+    one = cb.derived(torch.from_numpy(x[3]).cuda())            # one point -> (n_derived,)
+    assert tuple(one.shape) == (n_derived,)
+    np.testing.assert_array_equal(one.cpu().numpy(), f_arith(x[3:4], n_derived)[0])
+    assert cb.derived(x[3]).shape == (n_derived,)
+    with pytest.raises(ValueError):
+        cb.derived(np.zeros((4, n_dim + 1)))
+
+
+@pytest.mark.gpu
+@needs_hipcc
+def test_exp_and_log_give_equal_bits_in_every_layout_and_tile():
+    import tempest_amd as tp
+    need_gpu()
+    cb = tp.HipCallbacks(BASE + EXPLOG, 10, n_derived=2)
+    for n in SIZES:
+        x = points(n, 10, seed=50 + n)
+        got = all_layouts(cb, torch.from_numpy(x).cuda()).cpu().numpy()
+        assert np.all(np.isfinite(got))
+
+
+@pytest.mark.gpu
+@needs_hipcc
+@pytest.mark.parametrize("shift", [0, 1])
+def test_rows_past_n_are_never_written(shift):
+    """Guard cells round the output keep their fill, in both layouts and at every tile; shift 1 puts x and out on addresses that
+    are not 16-byte aligned (the 8-byte loads and stores of the row-major kernel)."""
+    import tempest_amd as tp
+    from tempest_amd.hipcallbacks import derived_tiles
+    need_gpu()
+    d, k, g = 10, 2, 64 + shift
+    cb = tp.HipCallbacks(BASE + ARITH, d, n_derived=k)
+    fill = -777.25
+    for n in (1, 63, 65, 257, 3001):
+        x = points(n, d, seed=n)
+        want = f_arith(x, k)
+        xbuf = torch.zeros(g + n * d + g, dtype=torch.float64, device="cuda")
+        xbuf[g:g + n * d] = torch.from_numpy(x).cuda().reshape(-1)
+        stream = cb._stream(xbuf)
+        for tile in (0,) + derived_tiles(d, k) + (1,):
+            obuf = torch.full((g + n * k + g,), fill, dtype=torch.float64, device="cuda")
+            rc = cb.lib.tphu_derived(stream, xbuf.data_ptr() + 8 * g, n, d, obuf.data_ptr() + 8 * g, k, 1, tile)
+            assert rc == 0, cb.lib.tphu_last_error()
+            o = obuf.cpu().numpy()
+            assert np.all(o[:g] == fill) and np.all(o[g + n * k:] == fill), (n, tile)
+            np.testing.assert_array_equal(o[g:g + n * k].reshape(n, k), want)
+        # dimension-major with leading dimensions larger than n
+        ld = n + 5
+        xs = torch.zeros((d, ld), dtype=torch.float64, device="cuda")
+        xs[:, :n] = torch.from_numpy(x.T.copy()).cuda()
+        os_ = torch.full((k, ld), fill, dtype=torch.float64, device="cuda")
+        assert cb.lib.tphu_derived(stream, xs.data_ptr(), n, ld, os_.data_ptr(), ld, 0, 0) == 0
+        o = os_.cpu().numpy()
+        assert np.all(o[:, n:] == fill)
+        np.testing.assert_array_equal(o[:, :n].T, want)
+    # checked arguments
+    assert cb.lib.tphu_derived(stream, xbuf.data_ptr(), 4, d + 1, obuf.data_ptr(), k, 1, 0) == -2
+    assert b"contiguous" in cb.lib.tphu_last_error()
+    assert cb.lib.tphu_derived(stream, xbuf.data_ptr(), 4, d, obuf.data_ptr(), k, 1, 32) == -2
+    assert cb.lib.tphu_derived(stream, None, 4, d, obuf.data_ptr(), k, 1, 0) == -2
+
+
+@pytest.mark.gpu
+@needs_hipcc
+def test_derived_reads_the_data_table_in_both_data_forms():
+    import tempest_amd as tp
+    need_gpu()
+    for cb in (tp.HipCallbacks(WHOLE_D + DERIVED_D, 3, data={"tab": TAB}, n_derived=2),
+               tp.HipCallbacks(TERM_D + DERIVED_D, 3, data={"tab": TAB}, n_terms="tab", n_derived=2)):
+        for n in (65, 700):
+            x = points(n, 3, seed=n)
+            got = all_layouts(cb, torch.from_numpy(x).cuda())
+            np.testing.assert_array_equal(got.cpu().numpy(), f_table(x, 2))
+        np.testing.assert_array_equal(cb.derived(x), f_table(x, 2))
+
+
+@pytest.mark.gpu
+@needs_hipcc
+def test_derived_respects_the_stream_it_is_given():
+    import tempest_amd as tp
+    need_gpu()
+    a = tp.HipCallbacks(BASE + ARITH, 10, n_derived=2)
+    b = tp.HipCallbacks(BASE + ARITH, 10, n_derived=2)
+    assert a.path == b.path
+    x = points(200_000, 10)
+    xt = torch.from_numpy(x).cuda()
+    want = f_arith(x, 2)
+    sa, sb = torch.cuda.Stream(), torch.cuda.Stream()
+    torch.cuda.synchronize()
+    outs = []
+    for rep in range(6):
+        with torch.cuda.stream(sa):
+            ya = xt * 1.0                                      # produced on sa: derived must queue behind it on sa
+            ra = a.derived(ya)
+        with torch.cuda.stream(sb):
+            yb = xt + 0.0
+            rb = b.derived(yb.T.contiguous().T)
+        outs.append((ra, rb, ya, yb))
+    torch.cuda.synchronize()
+    for ra, rb, _, _ in outs:
+        np.testing.assert_array_equal(ra.cpu().numpy(), want)
+        np.testing.assert_array_equal(rb.cpu().numpy(), want)
+
+
+def run_sampler(tp, cb, d=4, seed=4, **kw):
+    s = tp.Sampler(cb.prior_transform, cb.log_likelihood, d, n_particles=512, vectorize=True, clustering=False,
+                   random_state=seed, **kw)
+    s.run(n_total=2048, progress=False)
+    return s
+
+
+POSTERIOR_CASES = [dict(resample=r, trim_importance_weights=t) for r in (False, True) for t in (True, False)]
+
+
+@pytest.mark.gpu
+@needs_hipcc
+def test_whole_run_returns_derived_blobs_and_changes_nothing_else():
+    import tempest_amd as tp
+    need_gpu()
+    d, k = 4, 2
+    plain = run_sampler(tp, tp.HipCallbacks(BASE, d))
+    cb = tp.HipCallbacks(BASE + ARITH, d, n_derived=k)
+    s = run_sampler(tp, cb)
+    assert s._core.callbacks.hip_plugin is cb
+    for case in POSTERIOR_CASES:
+        np.random.seed(3)                                      # (resample=True draws its offset from NumPy's global stream)
+        x0, w0, l0 = plain.posterior(**case)
+        np.random.seed(3)
+        assert len(plain.posterior(return_blobs=True, **case)) == 3          # no derived function: the 3-tuple, as ever
+        np.random.seed(3)
+        x, w, logl, blobs = s.posterior(return_blobs=True, **case)
+        for got, want in ((x, x0), (w, w0), (logl, l0)):
+            np.testing.assert_array_equal(got, want)
+        assert blobs.shape == (len(x), k) and blobs.dtype == np.float64 and blobs.flags["C_CONTIGUOUS"]
+        np.testing.assert_array_equal(blobs, f_arith(x, k))
+        np.random.seed(3)
+        three = s.posterior(**case)
+        assert len(three) == 3
+        np.testing.assert_array_equal(three[0], x0)
+    x, w, logl, blobs, logw = s.posterior(return_blobs=True, return_logw=True)
+    assert blobs.shape == (len(x), k) and logw.ndim == 1
+
+
+@pytest.mark.gpu
+@needs_hipcc
+def test_sampler_derived_callable_torch_numpy_and_one_column():
+    import tempest_amd as tp
+    need_gpu()
+    d = 4
+    mean = torch.linspace(-1, 1, d, dtype=torch.float64, device="cuda")
+    seen = []
+
+    def f_torch(x):
+        seen.append(type(x))
+        return f_arith_torch(x, 3)
+
+    s = tp.Sampler(lambda u: 10 * u - 5, lambda x: -0.5 * ((x - mean) ** 2).sum(dim=1), d, n_particles=512, vectorize=True,
+                   clustering=False, random_state=2, derived=f_torch)
+    s.run(n_total=2048, progress=False)
+    assert not seen                                            # nothing calls it but posterior(return_blobs=True)
+    assert len(s.posterior()) == 3 and not seen
+    for case in POSTERIOR_CASES:
+        x, w, logl, blobs = s.posterior(return_blobs=True, **case)
+        np.testing.assert_array_equal(blobs, f_arith(x, 3))
+    assert seen and all(t is torch.Tensor for t in seen)
+    # one column -> (M,), from an (n, 1) and from an (n,) result; a HipCallbacks likelihood with an explicit derived=
+    cb = tp.HipCallbacks(BASE, d)
+    for fn in (lambda x: x[:, 0:1] + x[:, 1:2], lambda x: x[:, 0] + x[:, 1]):
+        s1 = run_sampler(tp, cb, derived=fn)
+        x, w, logl, blobs = s1.posterior(return_blobs=True)
+        assert blobs.shape == (len(x),)
+        np.testing.assert_array_equal(blobs, x[:, 0] + x[:, 1])
+    # NumPy callbacks: the derived function gets a NumPy array
+    kinds = []
+
+    def f_np(x):
+        kinds.append(type(x))
+        return f_arith(x, 2)
+
+    mh = mean.cpu().numpy()
+    s2 = tp.Sampler(lambda u: 10 * u - 5, lambda x: -0.5 * ((x - mh) ** 2).sum(axis=1), d, n_particles=256, vectorize=True,
+                    clustering=False, random_state=2, backend="numpy", derived=f_np)
+    s2.run(n_total=512, progress=False)
+    x, w, logl, blobs = s2.posterior(return_blobs=True)
+    np.testing.assert_array_equal(blobs, f_arith(x, 2))
+    assert kinds and all(t is np.ndarray for t in kinds)
+
+
+@pytest.mark.gpu
+@needs_hipcc
+def test_blobs_after_load_state_come_from_the_loaded_rows(tmp_path):
+    import tempest_amd as tp
+    need_gpu()
+    d, k = 4, 2
+    cb = tp.HipCallbacks(BASE + ARITH, d, n_derived=k)
+    s = run_sampler(tp, cb)
+    want = s.posterior(return_blobs=True, trim_importance_weights=False)
+    for name in ("run.state", "run.ckpt"):
+        s.save_state(tmp_path / name)
+        listing = [p.name for p in tmp_path.rglob("*")]
+        assert not any("blob" in n or "derived" in n for n in listing), listing
+        t = tp.Sampler(cb.prior_transform, cb.log_likelihood, d, n_particles=512, vectorize=True, clustering=False, random_state=4)
+        t.load_state(tmp_path / name)
+        got = t.posterior(return_blobs=True, trim_importance_weights=False)
+        assert len(got) == 4 and got[3].shape == (len(got[0]), k)
+        np.testing.assert_array_equal(got[0], want[0])         # the loaded rows are the saved rows (the weights are recomputed
+        np.testing.assert_array_equal(got[2], want[2])         # over the reloaded history and may differ in the last bits)
+        np.testing.assert_array_equal(got[3], f_arith(got[0], k))
+        got = t.posterior(return_blobs=True)
+        np.testing.assert_array_equal(got[3], f_arith(got[0], k))
+
+
+def _free_port():
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    p = s.getsockname()[1]
+    s.close()
+    return p
+
+
+@pytest.mark.gpu
+@needs_hipcc
+def test_two_ranks_return_the_same_derived_blobs(tmp_path):
+    need_gpu()
+    import torch.multiprocessing as mp
+    import tempest_amd as tp
+    from tests._dist_workers_derived import D, K, derived_gpu_worker
+    tp.HipCallbacks(BASE, D), tp.HipCallbacks(BASE + ARITH, D, n_derived=K)          # compiled once, here: the ranks find them cached
+    mp.spawn(derived_gpu_worker, args=(2, _free_port(), str(tmp_path), BASE, ARITH), nprocs=2, join=True)
+    r0, r1 = (np.load(tmp_path / f"derived{r}.npz") for r in (0, 1))
+    meta = json.load(open(tmp_path / "derived0.json"))
+    assert meta["cases"] == 4 and meta["rows"][0] > 0
+    for i in range(meta["cases"]):
+        x, blobs = r0[f"x{i}"], r0[f"blobs{i}"]
+        assert blobs.shape == (len(x), K)
+        np.testing.assert_array_equal(blobs, f_arith(x, K))
+        for key in ("x", "w", "logl", "blobs"):
+            np.testing.assert_array_equal(r0[f"{key}{i}"], r1[f"{key}{i}"])                  # every rank the same
+        for key in ("x", "w", "logl"):
+            np.testing.assert_array_equal(r0[f"{key}{i}"], r0[f"plain_{key}{i}"])            # and what a run without derived returns

@@ -315,11 +315,7 @@ class SamplerCore:
         if comm is None or not comm.active:
             # single shard: threshold, compaction, resampling and the gather into row-major (M, d) stay on the device;
             # only the M returned rows cross PCIe
-            sel, m_sel, wdiv = None, ctx.size, 1.0
-            if trim_importance_weights:
-                thr_dev, out = ctx.trim_threshold(w_dev, ess_trim, bins_trim, sync=True)
-                m_sel, wdiv = int(out[2]), float(out[1])
-                sel = ctx.compact_indices(w_dev, thr_dev[0:1], m_sel)
+            sel, m_sel, wdiv = self._select_rows(w_dev, trim_importance_weights, ess_trim, bins_trim)
             if resample:
                 from .tools import SQRTEPS
                 _, _, w_sel = ctx.posterior_rows(sel, m_sel, w=w_dev, wdiv=wdiv)
@@ -383,6 +379,40 @@ class SamplerCore:
         if return_logw:
             out.append(logw)
         return tuple(out)
+
+    def _select_rows(self, w_dev, trim_importance_weights, ess_trim, bins_trim):
+        """One shard: (sel, m_sel, wdiv) -- the device indices of the rows the posterior keeps (None: all of them), how many, and
+        what their weights are divided by -- from the trim threshold and the compaction, both on the device."""
+        ctx = self.state.ctx
+        sel, m_sel, wdiv = None, ctx.size, 1.0
+        if trim_importance_weights:
+            thr_dev, out = ctx.trim_threshold(w_dev, ess_trim, bins_trim, sync=True)
+            m_sel, wdiv = int(out[2]), float(out[1])
+            sel = ctx.compact_indices(w_dev, thr_dev[0:1], m_sel)
+        return sel, m_sel, wdiv
+
+    def compute_predictive(self, quantiles=(0.025, 0.5, 0.975), trim_importance_weights=True, ess_trim=0.99, bins_trim=1000):
+        """Posterior predictive mean, variance and quantiles of the HipCallbacks source's predict(x, r) over the rows and weights
+        compute_posterior returns (same selection, on the device): the rows are gathered and reduced there, only the
+        (n_predict,) results reach the host."""
+        from ._lib import TempestHipError
+        from .hipcallbacks import HipCallbacks
+        owner = getattr(self.config.log_likelihood, "__self__", None)
+        if not isinstance(owner, HipCallbacks) or not owner.n_predict:
+            raise TempestHipError("Sampler.predictive: the likelihood is no HipCallbacks source that defines predict(...) (give it and n_predict=)")
+        st = self.state
+        if st.comm is not None and st.comm.active:
+            raise NotImplementedError("Sampler.predictive is not available on a sharded run yet: every rank holds a part of the rows, and "
+                                      "folding per-rank partial sums and bucket totals is not built (DESIGN.md section 10)")
+        ctx = st.ctx
+        ctx.use_current_stream()
+        if owner.device is None:
+            owner.device = st.device
+        m, s1, _ = st.reweight_eval([1.0])[0]
+        w_dev = ctx.weights(1.0, m, s1)
+        sel, m_sel, wdiv = self._select_rows(w_dev, trim_importance_weights, ess_trim, bins_trim)
+        x_dev, _, w_sel = ctx.posterior_rows(sel, m_sel, w=w_dev, wdiv=wdiv)
+        return owner.predictive(x_dev, w_sel, quantiles)
 
     def _derived_fn(self):
         """rows (M, d) on the device -> the derived quantities as a host (M, k) float64 array, or None without a derived function:

@@ -85,6 +85,20 @@ DERIVED_TILES = (256, 128, 64)
 DERIVED_LDS_BYTES = 65536
 _RESERVED = ("n_terms",)
 
+# predict(x, r): the order of the sums over rows behind predictive()'s mean and var -- chunks of PREDICT_SUM_LAYOUT[0] consecutive
+# rows (a wave: its 64 values are added by the shuffle tree v[:h] + v[h:2h], h = 32, 16, ... 1), blocks of PREDICT_SUM_LAYOUT[1]
+# consecutive chunk sums in chunk order, the block sums in block order.  Design constants of the template.
+PREDICT_SUM_LAYOUT = (64, 16)
+MAX_QUANTILES = 8
+PREDICT_MAX_TILE = 64              # indices per workgroup, at most (TPHU_PRED_RT)
+PREDICT_TABLES = 24                # (index, quantile) bucket tables a workgroup of the select keeps in LDS (TPHU_PRED_TAB)
+# Tile rule of predictive(): halve the indices per workgroup from 64 while the moment kernel's grid -- row blocks x index tiles -- has
+# fewer workgroups than this (4 per CU of a 256-CU device), and cut the rows into as many slabs for the select as bring its grid
+# there.  Chosen by that count alone, WITHOUT a run of tools/bench_predictive.py on the device behind it; the tile and the slab
+# decide time only, never a bit of the result.
+PREDICT_MIN_WORKGROUPS = 1024
+PREDICT_SCRATCH_WORDS = 1 << 23    # 64 MiB of batch scratch at most: more indices than fit go through in batches
+
 
 def prefer_split(n: int, n_terms: int) -> bool:
     for t_min, n_below in DATA_LIKE_THRESHOLDS["bands"]:
@@ -102,6 +116,48 @@ def derived_tiles(n_dim: int, n_derived: int):
 def _has_derived(source: str) -> bool:
     """The source DEFINES derived (`void derived(`): the word alone, in a comment or a name, is not a definition."""
     return re.search(r"\bvoid\s+derived\s*\(", source) is not None
+
+
+def _has_predict(source: str) -> bool:
+    """The source DEFINES predict (`double predict(`): the word alone, in a comment or a name, is not a definition."""
+    return re.search(r"\bdouble\s+predict\s*\(", source) is not None
+
+
+def _check_n_predict(source, n_predict, host) -> int:
+    has = _has_predict(source)
+    if n_predict is None:
+        if has:
+            raise ValueError("HipCallbacks: the source defines predict(...): give n_predict= (an int, or the name of a data entry)")
+        return 0
+    if not has:
+        raise ValueError("HipCallbacks: n_predict= goes with a source that defines __device__ double predict(const double* x, int64_t r)")
+    if isinstance(n_predict, str):
+        if n_predict not in host:
+            raise ValueError(f"HipCallbacks: n_predict={n_predict!r} names no data entry")
+        return int(host[n_predict].shape[0])
+    if isinstance(n_predict, bool) or not isinstance(n_predict, (int, np.integer)) or not 0 < int(n_predict) < 2 ** 31:
+        raise ValueError(f"HipCallbacks: n_predict must be a positive int or the name of a data entry, got {n_predict!r}")
+    return int(n_predict)
+
+
+def predict_tiles(n: int, n_predict: int, n_q: int):
+    """(indices per workgroup, rows per workgroup of the select) predictive() launches with: the rule of PREDICT_MIN_WORKGROUPS."""
+    span = PREDICT_SUM_LAYOUT[0] * PREDICT_SUM_LAYOUT[1]
+    n_blocks = -(-n // span)
+    tile = PREDICT_MAX_TILE
+    while tile > 1 and n_blocks * -(-n_predict // tile) < PREDICT_MIN_WORKGROUPS:
+        tile //= 2
+    rts = max(1, min(tile, PREDICT_TABLES // max(1, n_q)))
+    slabs = max(1, min(-(-n // 256), -(-PREDICT_MIN_WORKGROUPS // -(-n_predict // rts))))
+    return tile, max(256, -(-(-(-n // slabs)) // 256) * 256, -(-(-(-n // 65535)) // 256) * 256)
+
+
+def predict_scratch_words(n: int, n_predict: int, n_q: int) -> int:
+    """8-byte words of scratch tphu_predictive gets for this call: W and the block sums of w, and for a batch of indices the block
+    sums, bucket totals, prefixes, targets and NaN flags -- all n_predict indices, or as many as PREDICT_SCRATCH_WORDS hold."""
+    n_blocks = -(-n // (PREDICT_SUM_LAYOUT[0] * PREDICT_SUM_LAYOUT[1]))
+    per_r = n_blocks + 258 * n_q + 1
+    return 1 + n_blocks + per_r * min(n_predict, max(1, PREDICT_SCRATCH_WORDS // per_r))
 
 
 def _check_n_derived(source, n_derived) -> int:
@@ -177,16 +233,17 @@ def _struct_text(tables) -> str:
     return "\n".join(lines)
 
 
-def plugin_source(source: str, tables=None, term: bool = False, *, derived: bool = False) -> str:
+def plugin_source(source: str, tables=None, term: bool = False, *, derived: bool = False, predict: bool = False) -> str:
     """The translation unit for `source`.  tables None: callbacks of x alone (the template as it always was, byte for byte);
     ((name, rank), ...): the callbacks take `const tphu_data& D` and every kernel and entry point carries the table;
     term: the source gives log_likelihood_term and the library owns the sum; derived: the source gives derived(x, out) and the
-    plugin gets k_user_derived / tphu_derived (compiled with -DN_DERIVED=k)."""
+    plugin gets k_user_derived / tphu_derived (compiled with -DN_DERIVED=k); predict: the source gives predict(x, r) and the plugin
+    gets the k_user_predict_* kernels / tphu_predictive (compiled with -DTPHU_PREDICT)."""
     text = _TEMPLATE.read_text()
     if term and tables is None:
         tables = ()
-    # lines of the data / term form / a source with derived() only: dropped whole otherwise
-    keep = {"//@D": tables is not None, "//@T": term, "//@X": derived}
+    # lines of the data / term form / a source with derived() / with predict() only: dropped whole otherwise
+    keep = {"//@D": tables is not None, "//@T": term, "//@X": derived, "//@P": predict}
     out = []
     for line in text.split("\n"):
         if line[:4] in keep and line[4:5] in ("", " "):
@@ -204,6 +261,8 @@ def plugin_source(source: str, tables=None, term: bool = False, *, derived: bool
         text = text.replace("@DATA_STRUCT@", _struct_text(tables))
     if term:
         text = text.replace("@TPHU_CHUNK@", str(SUM_LAYOUT[0])).replace("@TPHU_BLOCK@", str(SUM_LAYOUT[1]))
+    if predict:
+        text = text.replace("@TPHU_PCHUNK@", str(PREDICT_SUM_LAYOUT[0])).replace("@TPHU_PBLOCK@", str(PREDICT_SUM_LAYOUT[1]))
     return text.replace("@USER_SOURCE@", source)
 
 
@@ -223,15 +282,18 @@ def _toolchain_id() -> str:
     return _TOOLCHAIN
 
 
-def build_plugin(source: str, n_dim: int, verbose: bool = False, tables=None, term: bool = False, *, n_derived: int = 0) -> Path:
+def build_plugin(source: str, n_dim: int, verbose: bool = False, tables=None, term: bool = False, *, n_derived: int = 0,
+                 predict: bool = False) -> Path:
     """Compile (or find in the cache) the plugin for `source`; returns the path of the shared library.  `tables` / `term` as in
     plugin_source: names, ranks and the element type of the data entries are in the generated text and so in the key; values and
     extents are not -- one compile serves every data set of that shape of table.  n_derived > 0: the source has derived(); only then
-    do -DN_DERIVED and its part of the key exist, so every other source keeps the file name it had."""
-    text = plugin_source(source, tables, term, derived=n_derived > 0)
-    defs = [f"-DN_DIM={int(n_dim)}"] + ([f"-DN_DERIVED={int(n_derived)}"] if n_derived > 0 else [])
+    do -DN_DERIVED and its part of the key exist, so every other source keeps the file name it had; the same holds for predict
+    (the source has predict()): -DTPHU_PREDICT and "|predict" in the key only then."""
+    text = plugin_source(source, tables, term, derived=n_derived > 0, predict=predict)
+    defs = [f"-DN_DIM={int(n_dim)}"] + ([f"-DN_DERIVED={int(n_derived)}"] if n_derived > 0 else []) + (["-DTPHU_PREDICT"] if predict else [])
     deps = (_CSRC / "common.h").read_bytes() + (_CSRC.parent.parent / "include" / "tempest_hip.h").read_bytes()
-    key = f"|{n_dim}|{_ARCH}|{' '.join(_FLAGS)}|{_toolchain_id()}" + (f"|derived={int(n_derived)}" if n_derived > 0 else "")
+    key = f"|{n_dim}|{_ARCH}|{' '.join(_FLAGS)}|{_toolchain_id()}" + (f"|derived={int(n_derived)}" if n_derived > 0 else "") \
+        + ("|predict" if predict else "")
     tag = hashlib.sha256(text.encode() + deps + key.encode()).hexdigest()[:20]
     name = f"tphu_{n_dim}d_{tag}.so"
     for d in _cache_dirs():
@@ -264,10 +326,11 @@ class HipCallbacks:
     # a source of x alone: no tables, no term form (class defaults; __init__ fills them in where `data=` / `n_terms=` are given)
     term, tables, n_terms, data_like, split_tile, sum_layout = False, None, 0, None, 0, SUM_LAYOUT
     n_derived, derived_tile = 0, 0
-    _device = _dev_tables = _dstruct = _bsum = None
+    n_predict, predict_tile, predict_sum_layout = 0, 0, PREDICT_SUM_LAYOUT
+    _device = _dev_tables = _dstruct = _bsum = _pscratch = None
 
     def __init__(self, source: str, n_dim: int, fused: bool = True, verbose: bool = False, whole_step: bool = True,
-                 persistent: bool = False, data=None, n_terms=None, n_derived=None):
+                 persistent: bool = False, data=None, n_terms=None, n_derived=None, n_predict=None):
         if not isinstance(n_dim, int) or n_dim <= 0:
             raise ValueError(f"n_dim must be a positive int, got {n_dim!r}")
         for fn in ("prior_transform", "log_likelihood"):
@@ -286,6 +349,10 @@ class HipCallbacks:
         self.tables, self._host = (None, {}) if data is None else _table_spec(data)
         if has_term and self.tables is None:
             self.tables = ()
+        self.n_predict = _check_n_predict(source, n_predict, self._host)
+        # > 0 pins the indices per workgroup of predictive() (1 .. 64); (tile, slab) also the rows per workgroup of its select
+        self.predict_tile = 0
+        self._pscratch = None
         self.n_terms = 0
         if has_term:
             if isinstance(n_terms, str):
@@ -316,7 +383,7 @@ class HipCallbacks:
         env = os.environ.get("TEMPEST_AMD_PERSISTENT")
         self.persistent = bool(persistent) if env is None else env != "0"
         self.run_groups = 0                    # > 0 limits the workgroups of that launch (tests: several tiles per workgroup)
-        self.path = build_plugin(source, n_dim, verbose, self.tables, self.term, n_derived=self.n_derived)
+        self.path = build_plugin(source, n_dim, verbose, self.tables, self.term, n_derived=self.n_derived, predict=bool(self.n_predict))
         import torch  # noqa: F401  (its HIP runtime must be the one in the process, as for libtempest_hip)
         lib = C.CDLL(str(self.path))
         ptr, i64 = C.c_void_p, C.c_int64
@@ -335,6 +402,10 @@ class HipCallbacks:
             lib.tphu_derived.argtypes = [ptr, ptr, i64, i64, ptr, i64, C.c_int, C.c_int]
             fns.append(lib.tphu_derived)
             lib.tphu_n_derived.restype = lib.tphu_derived_rows.restype = C.c_int
+        if self.n_predict:
+            lib.tphu_predictive.argtypes = [ptr, ptr, ptr, i64, i64, ptr, C.c_int, ptr, ptr, i64, C.c_int, i64]
+            fns.append(lib.tphu_predictive)
+            lib.tphu_predict_layout.argtypes, lib.tphu_predict_layout.restype = [C.c_int], C.c_int
         if self.tables is not None:            # a data-carrying plugin: every entry point takes the host copy of tphu_data last
             for f in fns:
                 f.argtypes = list(f.argtypes) + [ptr]
@@ -357,6 +428,8 @@ class HipCallbacks:
         if self.n_derived and (lib.tphu_n_derived() != self.n_derived
                                or lib.tphu_derived_rows() != (derived_tiles(n_dim, self.n_derived) or (0,))[0]):
             raise TempestHipError(f"plugin {self.path}: derived() shape or tile rule does not match this package")
+        if self.n_predict and tuple(lib.tphu_predict_layout(i) for i in range(4)) != PREDICT_SUM_LAYOUT + (PREDICT_MAX_TILE, PREDICT_TABLES):
+            raise TempestHipError(f"plugin {self.path}: predict() sum layout or tile limits do not match this package")
         self.lib = lib
 
     # ---------------------------------------------------------------------------------- data tables
@@ -497,13 +570,13 @@ class HipCallbacks:
         ll = ll[0] if one else ll
         return ll.cpu().numpy() if was_np else ll
 
-    def _on_table_device(self, t):
+    def _on_table_device(self, t, what="derived"):
         """The data tables are pointers into ONE device's memory: rows on another device must not meet them in a kernel."""
         if self.tables:
             self._data()
             tab = next(iter(self._dev_tables.values()))
             if tab.device != t.device:
-                raise ValueError(f"HipCallbacks.derived: the points are on {t.device}, the data tables on {tab.device}")
+                raise ValueError(f"HipCallbacks.{what}: the points are on {t.device}, the data tables on {tab.device}")
 
     def derived(self, x):
         """(n, n_dim) points [or one point] -> (n, n_derived) values of the source's derived() [or (n_derived,)], same container
@@ -542,6 +615,52 @@ class HipCallbacks:
             out = outs.T
         out = out[0] if one else out
         return out.cpu().numpy() if was_np else out
+
+    def predictive(self, x, w, quantiles=(0.025, 0.5, 0.975)):
+        """Posterior predictive of the source's predict(x, r), r = 0 .. n_predict - 1, over the (n, n_dim) points x with weights w
+        (n; >= 0, finite, positive sum, not necessarily normalised; torch-ROCm tensors or NumPy arrays): a dict of NumPy arrays
+        "mean", "var" (n_predict,), "quantiles" (len(quantiles), n_predict) -- the weighted inverted CDF, always one of the
+        predictions -- and "n_rows", "ess" = (sum w)^2 / sum w^2.  Nothing of size n x n_predict is formed; only the results come
+        to the host.  The scratch is one buffer kept on this object (like the split likelihood's): calls on
+        the same object from two streams at once would share it -- give each stream its own HipCallbacks object (same plugin)."""
+        import torch
+        if not self.n_predict:
+            raise TempestHipError("HipCallbacks.predictive: the source defines no predict(...) (give it and n_predict=)")
+        qs = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
+        if qs.ndim != 1 or len(qs) > MAX_QUANTILES or not np.all((qs >= 0.0) & (qs <= 1.0)):
+            raise ValueError(f"predictive: quantiles must be at most {MAX_QUANTILES} numbers in [0, 1], got {quantiles!r}")
+        dev = self._device or torch.device("cuda", torch.cuda.current_device())
+
+        def on_device(a):
+            if not isinstance(a, torch.Tensor):
+                a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64))
+            if not a.is_cuda:
+                a = a.to(dev)
+            return a.to(torch.float64).contiguous()
+        x, w = on_device(x), on_device(w)
+        if x.dim() != 2 or x.shape[1] != self.n_dim or x.shape[0] == 0:
+            raise ValueError(f"predictive: expected (n, {self.n_dim}) points with n > 0, got {tuple(x.shape)}")
+        n = x.shape[0]
+        if w.dim() != 1 or w.shape[0] != n or w.device != x.device:
+            raise ValueError(f"predictive: expected ({n},) weights beside the points, got {tuple(w.shape)} on {w.device}")
+        s1, s2, bad = (float(v) for v in torch.stack([w.sum(), (w * w).sum(), (~(torch.isfinite(w) & (w >= 0))).sum().double()]).cpu())
+        if bad or not s1 > 0.0 or not np.isfinite(s1):
+            raise ValueError("predictive: the weights must be finite, >= 0 and have a positive sum")
+        self._on_table_device(x, "predictive")
+        R, nq = self.n_predict, len(qs)
+        pin = self.predict_tile
+        tile, slab = predict_tiles(n, R, nq)
+        if pin:
+            tile, slab = (int(pin[0]), int(pin[1])) if isinstance(pin, (tuple, list)) else (int(pin), slab)
+        words = predict_scratch_words(n, R, nq)
+        if self._pscratch is None or self._pscratch.numel() < words or self._pscratch.device != x.device:
+            self._pscratch = torch.empty(words, dtype=torch.int64, device=x.device)      # kept: no allocation per call
+        out = torch.empty((2 + nq, R), dtype=torch.float64, device=x.device)
+        self._check(self.lib.tphu_predictive(self._stream(x), x.data_ptr(), w.data_ptr(), n, R, qs.ctypes.data, nq, out.data_ptr(),
+                                             self._pscratch.data_ptr(), self._pscratch.numel(), tile, slab, *self._data()),
+                    "tphu_predictive")
+        res = out.cpu().numpy()
+        return {"mean": res[0].copy(), "var": res[1].copy(), "quantiles": res[2:].copy(), "n_rows": n, "ess": s1 * s1 / s2}
 
     # ------------------------------------------------------------------------------ fused MCMC step
     def accept(self, kernel_id, beta, u, x, logl, uprime, maha_u, maha_up, assign, K, dof, seed, tick, item0, sums,

@@ -136,6 +136,14 @@ class Sampler:
                                             trim_importance_weights=trim_importance_weights, return_logw=return_logw,
                                             ess_trim=ess_trim, bins_trim=bins_trim)
 
+    def predictive(self, quantiles=(0.025, 0.5, 0.975), trim_importance_weights: bool = True, ess_trim: float = 0.99,
+                   bins_trim: int = 1000) -> dict:
+        """Posterior predictive of a HipCallbacks source's predict(x, r), r = 0 .. n_predict - 1, over the weighted rows posterior()
+        returns: {"mean", "var": (n_predict,), "quantiles": (len(quantiles), n_predict), "n_rows", "ess"}, NumPy.  The rows stay on
+        the device; nothing of size rows x n_predict is formed.  Not available on a sharded run (NotImplementedError)."""
+        return self._core.compute_predictive(quantiles=quantiles, trim_importance_weights=trim_importance_weights,
+                                             ess_trim=ess_trim, bins_trim=bins_trim)
+
     def evidence(self) -> tuple:
         """(logZ, None): the reference never computes an error estimate (core.py:151,244-247)."""
         return self._core.compute_evidence()

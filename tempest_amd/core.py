@@ -414,6 +414,30 @@ class SamplerCore:
         x_dev, _, w_sel = ctx.posterior_rows(sel, m_sel, w=w_dev, wdiv=wdiv)
         return owner.predictive(x_dev, w_sel, quantiles)
 
+    def compute_pointwise(self, trim_importance_weights=True, ess_trim=0.99, bins_trim=1000):
+        """Pointwise log predictive densities, WAIC and importance-sampling LOO of a pointwise-enabled HipCallbacks source over the
+        rows and weights compute_posterior returns (same selection, on the device): the rows are gathered and reduced there, only
+        the (n_terms,) results reach the host."""
+        from ._lib import TempestHipError
+        from .hipcallbacks import HipCallbacks
+        owner = getattr(self.config.log_likelihood, "__self__", None)
+        if not isinstance(owner, HipCallbacks) or not owner.pointwise_enabled:
+            raise TempestHipError("Sampler.pointwise: the likelihood is no HipCallbacks source built with pointwise=True (give it, with a "
+                                  "source that defines log_likelihood_term)")
+        st = self.state
+        if st.comm is not None and st.comm.active:
+            raise NotImplementedError("Sampler.pointwise is not available on a sharded run yet: every rank holds a part of the rows, and "
+                                      "folding per-rank maxima, minima and partial sums is not built (DESIGN.md section 10)")
+        ctx = st.ctx
+        ctx.use_current_stream()
+        if owner.device is None:
+            owner.device = st.device
+        m, s1, _ = st.reweight_eval([1.0])[0]
+        w_dev = ctx.weights(1.0, m, s1)
+        sel, m_sel, wdiv = self._select_rows(w_dev, trim_importance_weights, ess_trim, bins_trim)
+        x_dev, _, w_sel = ctx.posterior_rows(sel, m_sel, w=w_dev, wdiv=wdiv)
+        return owner.pointwise(x_dev, w_sel)
+
     def _derived_fn(self):
         """rows (M, d) on the device -> the derived quantities as a host (M, k) float64 array, or None without a derived function:
         config.derived, else the `derived` of the HipCallbacks object the likelihood belongs to."""

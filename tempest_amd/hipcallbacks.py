@@ -99,6 +99,14 @@ PREDICT_TABLES = 24                # (index, quantile) bucket tables a workgroup
 PREDICT_MIN_WORKGROUPS = 1024
 PREDICT_SCRATCH_WORDS = 1 << 23    # 64 MiB of batch scratch at most: more indices than fit go through in batches
 
+# pointwise(): its sums over rows run in PREDICT_SUM_LAYOUT too.  Tile rule: halve the indices per workgroup from 64 while the grid of
+# its two sweeps -- row blocks x index tiles -- has fewer workgroups than this (4 per CU of a 256-CU device).  Chosen by that count
+# alone, WITHOUT a timing on the device behind it; the tile decides time only, never a bit of the result.
+POINTWISE_MAX_TILE = 64            # indices per workgroup, at most (TPHU_PW_RT)
+POINTWISE_MIN_WORKGROUPS = 1024
+POINTWISE_SCRATCH_WORDS = 1 << 23  # 64 MiB of batch scratch at most: more indices than fit go through in batches
+POINTWISE_KEYS = ("lppd", "mean", "p_waic", "elpd_waic", "elpd_loo", "ess_loo")      # the rows of tphu_pointwise's output
+
 
 def prefer_split(n: int, n_terms: int) -> bool:
     for t_min, n_below in DATA_LIKE_THRESHOLDS["bands"]:
@@ -158,6 +166,23 @@ def predict_scratch_words(n: int, n_predict: int, n_q: int) -> int:
     n_blocks = -(-n // (PREDICT_SUM_LAYOUT[0] * PREDICT_SUM_LAYOUT[1]))
     per_r = n_blocks + 258 * n_q + 1
     return 1 + n_blocks + per_r * min(n_predict, max(1, PREDICT_SCRATCH_WORDS // per_r))
+
+
+def pointwise_tiles(n: int, n_terms: int) -> int:
+    """Indices per workgroup pointwise() launches with: the rule of POINTWISE_MIN_WORKGROUPS."""
+    n_blocks = -(-n // (PREDICT_SUM_LAYOUT[0] * PREDICT_SUM_LAYOUT[1]))
+    tile = POINTWISE_MAX_TILE
+    while tile > 1 and n_blocks * -(-n_terms // tile) < POINTWISE_MIN_WORKGROUPS:
+        tile //= 2
+    return tile
+
+
+def pointwise_scratch_words(n: int, n_terms: int) -> int:
+    """8-byte words of scratch tphu_pointwise gets for this call: W and the block sums of w, and for a batch of indices four arrays
+    of block values and the two shifts -- all n_terms indices, or as many as POINTWISE_SCRATCH_WORDS hold."""
+    n_blocks = -(-n // (PREDICT_SUM_LAYOUT[0] * PREDICT_SUM_LAYOUT[1]))
+    per_r = 4 * n_blocks + 2
+    return 1 + n_blocks + per_r * min(n_terms, max(1, POINTWISE_SCRATCH_WORDS // per_r))
 
 
 def _check_n_derived(source, n_derived) -> int:
@@ -233,17 +258,21 @@ def _struct_text(tables) -> str:
     return "\n".join(lines)
 
 
-def plugin_source(source: str, tables=None, term: bool = False, *, derived: bool = False, predict: bool = False) -> str:
+def plugin_source(source: str, tables=None, term: bool = False, *, derived: bool = False, predict: bool = False,
+                  pointwise: bool = False) -> str:
     """The translation unit for `source`.  tables None: callbacks of x alone (the template as it always was, byte for byte);
     ((name, rank), ...): the callbacks take `const tphu_data& D` and every kernel and entry point carries the table;
     term: the source gives log_likelihood_term and the library owns the sum; derived: the source gives derived(x, out) and the
     plugin gets k_user_derived / tphu_derived (compiled with -DN_DERIVED=k); predict: the source gives predict(x, r) and the plugin
-    gets the k_user_predict_* kernels / tphu_predictive (compiled with -DTPHU_PREDICT)."""
+    gets the k_user_predict_* kernels / tphu_predictive (compiled with -DTPHU_PREDICT); pointwise (term form only): the plugin gets
+    the k_user_pw_* kernels / tphu_pointwise (compiled with -DTPHU_POINTWISE)."""
     text = _TEMPLATE.read_text()
     if term and tables is None:
         tables = ()
-    # lines of the data / term form / a source with derived() / with predict() only: dropped whole otherwise
-    keep = {"//@D": tables is not None, "//@T": term, "//@X": derived, "//@P": predict}
+    # lines of the data / term form / a source with derived() / with predict() / with pointwise=True only: dropped whole otherwise
+    # (//@Q: what predict and pointwise share -- the layout constants, the row loads, the sum of the weights)
+    keep = {"//@D": tables is not None, "//@T": term, "//@X": derived, "//@P": predict, "//@W": pointwise,
+            "//@Q": predict or pointwise}
     out = []
     for line in text.split("\n"):
         if line[:4] in keep and line[4:5] in ("", " "):
@@ -261,7 +290,7 @@ def plugin_source(source: str, tables=None, term: bool = False, *, derived: bool
         text = text.replace("@DATA_STRUCT@", _struct_text(tables))
     if term:
         text = text.replace("@TPHU_CHUNK@", str(SUM_LAYOUT[0])).replace("@TPHU_BLOCK@", str(SUM_LAYOUT[1]))
-    if predict:
+    if predict or pointwise:
         text = text.replace("@TPHU_PCHUNK@", str(PREDICT_SUM_LAYOUT[0])).replace("@TPHU_PBLOCK@", str(PREDICT_SUM_LAYOUT[1]))
     return text.replace("@USER_SOURCE@", source)
 
@@ -283,17 +312,18 @@ def _toolchain_id() -> str:
 
 
 def build_plugin(source: str, n_dim: int, verbose: bool = False, tables=None, term: bool = False, *, n_derived: int = 0,
-                 predict: bool = False) -> Path:
+                 predict: bool = False, pointwise: bool = False) -> Path:
     """Compile (or find in the cache) the plugin for `source`; returns the path of the shared library.  `tables` / `term` as in
     plugin_source: names, ranks and the element type of the data entries are in the generated text and so in the key; values and
     extents are not -- one compile serves every data set of that shape of table.  n_derived > 0: the source has derived(); only then
     do -DN_DERIVED and its part of the key exist, so every other source keeps the file name it had; the same holds for predict
-    (the source has predict()): -DTPHU_PREDICT and "|predict" in the key only then."""
-    text = plugin_source(source, tables, term, derived=n_derived > 0, predict=predict)
-    defs = [f"-DN_DIM={int(n_dim)}"] + ([f"-DN_DERIVED={int(n_derived)}"] if n_derived > 0 else []) + (["-DTPHU_PREDICT"] if predict else [])
+    (the source has predict()): -DTPHU_PREDICT and "|predict" in the key only then; and for pointwise (-DTPHU_POINTWISE, "|pointwise")."""
+    text = plugin_source(source, tables, term, derived=n_derived > 0, predict=predict, pointwise=pointwise)
+    defs = [f"-DN_DIM={int(n_dim)}"] + ([f"-DN_DERIVED={int(n_derived)}"] if n_derived > 0 else []) + (["-DTPHU_PREDICT"] if predict else []) \
+        + (["-DTPHU_POINTWISE"] if pointwise else [])
     deps = (_CSRC / "common.h").read_bytes() + (_CSRC.parent.parent / "include" / "tempest_hip.h").read_bytes()
     key = f"|{n_dim}|{_ARCH}|{' '.join(_FLAGS)}|{_toolchain_id()}" + (f"|derived={int(n_derived)}" if n_derived > 0 else "") \
-        + ("|predict" if predict else "")
+        + ("|predict" if predict else "") + ("|pointwise" if pointwise else "")
     tag = hashlib.sha256(text.encode() + deps + key.encode()).hexdigest()[:20]
     name = f"tphu_{n_dim}d_{tag}.so"
     for d in _cache_dirs():
@@ -327,10 +357,12 @@ class HipCallbacks:
     term, tables, n_terms, data_like, split_tile, sum_layout = False, None, 0, None, 0, SUM_LAYOUT
     n_derived, derived_tile = 0, 0
     n_predict, predict_tile, predict_sum_layout = 0, 0, PREDICT_SUM_LAYOUT
-    _device = _dev_tables = _dstruct = _bsum = _pscratch = None
+    pointwise_enabled, pointwise_tile = False, 0
+    _device = _dev_tables = _dstruct = _bsum = _pscratch = _wscratch = None
 
     def __init__(self, source: str, n_dim: int, fused: bool = True, verbose: bool = False, whole_step: bool = True,
-                 persistent: bool = False, data=None, n_terms=None, n_derived=None, n_predict=None):
+                 persistent: bool = False, data=None, n_terms=None, n_derived=None, n_predict=None, *,
+                 pointwise=False):
         if not isinstance(n_dim, int) or n_dim <= 0:
             raise ValueError(f"n_dim must be a positive int, got {n_dim!r}")
         for fn in ("prior_transform", "log_likelihood"):
@@ -343,6 +375,13 @@ class HipCallbacks:
             raise ValueError("HipCallbacks: log_likelihood_term needs n_terms= (an int, or the name of a data entry)")
         if n_terms is not None and not has_term:
             raise ValueError("HipCallbacks: n_terms= goes with a source that defines log_likelihood_term")
+        if not isinstance(pointwise, (bool, np.bool_)):
+            raise ValueError(f"HipCallbacks: pointwise must be True or False, got {pointwise!r}")
+        if pointwise and not has_term:
+            raise ValueError("HipCallbacks: pointwise=True goes with a source that defines log_likelihood_term (and n_terms=)")
+        self.pointwise_enabled = bool(pointwise)
+        self.pointwise_tile = 0                # > 0 pins the indices per workgroup of pointwise() (1 .. 64)
+        self._wscratch = None
         self.n_derived = _check_n_derived(source, n_derived)
         self.derived_tile = 0                  # > 0 pins the row-major derived kernel: 256 / 128 / 64 rows per workgroup, 1 = direct
         self.term = has_term
@@ -383,7 +422,8 @@ class HipCallbacks:
         env = os.environ.get("TEMPEST_AMD_PERSISTENT")
         self.persistent = bool(persistent) if env is None else env != "0"
         self.run_groups = 0                    # > 0 limits the workgroups of that launch (tests: several tiles per workgroup)
-        self.path = build_plugin(source, n_dim, verbose, self.tables, self.term, n_derived=self.n_derived, predict=bool(self.n_predict))
+        self.path = build_plugin(source, n_dim, verbose, self.tables, self.term, n_derived=self.n_derived, predict=bool(self.n_predict),
+                                 pointwise=self.pointwise_enabled)
         import torch  # noqa: F401  (its HIP runtime must be the one in the process, as for libtempest_hip)
         lib = C.CDLL(str(self.path))
         ptr, i64 = C.c_void_p, C.c_int64
@@ -406,6 +446,10 @@ class HipCallbacks:
             lib.tphu_predictive.argtypes = [ptr, ptr, ptr, i64, i64, ptr, C.c_int, ptr, ptr, i64, C.c_int, i64]
             fns.append(lib.tphu_predictive)
             lib.tphu_predict_layout.argtypes, lib.tphu_predict_layout.restype = [C.c_int], C.c_int
+        if self.pointwise_enabled:
+            lib.tphu_pointwise.argtypes = [ptr, ptr, ptr, i64, i64, ptr, ptr, i64, C.c_int]
+            fns.append(lib.tphu_pointwise)
+            lib.tphu_pointwise_layout.argtypes, lib.tphu_pointwise_layout.restype = [C.c_int], C.c_int
         if self.tables is not None:            # a data-carrying plugin: every entry point takes the host copy of tphu_data last
             for f in fns:
                 f.argtypes = list(f.argtypes) + [ptr]
@@ -430,6 +474,8 @@ class HipCallbacks:
             raise TempestHipError(f"plugin {self.path}: derived() shape or tile rule does not match this package")
         if self.n_predict and tuple(lib.tphu_predict_layout(i) for i in range(4)) != PREDICT_SUM_LAYOUT + (PREDICT_MAX_TILE, PREDICT_TABLES):
             raise TempestHipError(f"plugin {self.path}: predict() sum layout or tile limits do not match this package")
+        if self.pointwise_enabled and tuple(lib.tphu_pointwise_layout(i) for i in range(3)) != PREDICT_SUM_LAYOUT + (POINTWISE_MAX_TILE,):
+            raise TempestHipError(f"plugin {self.path}: pointwise sum layout or tile limit does not match this package")
         self.lib = lib
 
     # ---------------------------------------------------------------------------------- data tables
@@ -616,6 +662,30 @@ class HipCallbacks:
         out = out[0] if one else out
         return out.cpu().numpy() if was_np else out
 
+    def _rows_and_weights(self, x, w, what):
+        """The (n, n_dim) points and (n,) weights of predictive() / pointwise() as contiguous float64 device tensors, checked: n > 0,
+        weights finite, >= 0, with a positive sum.  Returns (x, w, n, sum w, sum w^2)."""
+        import torch
+        dev = self._device or torch.device("cuda", torch.cuda.current_device())
+
+        def on_device(a):
+            if not isinstance(a, torch.Tensor):
+                a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64))
+            if not a.is_cuda:
+                a = a.to(dev)
+            return a.to(torch.float64).contiguous()
+        x, w = on_device(x), on_device(w)
+        if x.dim() != 2 or x.shape[1] != self.n_dim or x.shape[0] == 0:
+            raise ValueError(f"{what}: expected (n, {self.n_dim}) points with n > 0, got {tuple(x.shape)}")
+        n = x.shape[0]
+        if w.dim() != 1 or w.shape[0] != n or w.device != x.device:
+            raise ValueError(f"{what}: expected ({n},) weights beside the points, got {tuple(w.shape)} on {w.device}")
+        s1, s2, bad = (float(v) for v in torch.stack([w.sum(), (w * w).sum(), (~(torch.isfinite(w) & (w >= 0))).sum().double()]).cpu())
+        if bad or not s1 > 0.0 or not np.isfinite(s1):
+            raise ValueError(f"{what}: the weights must be finite, >= 0 and have a positive sum")
+        self._on_table_device(x, what)
+        return x, w, n, s1, s2
+
     def predictive(self, x, w, quantiles=(0.025, 0.5, 0.975)):
         """Posterior predictive of the source's predict(x, r), r = 0 .. n_predict - 1, over the (n, n_dim) points x with weights w
         (n; >= 0, finite, positive sum, not necessarily normalised; torch-ROCm tensors or NumPy arrays): a dict of NumPy arrays
@@ -629,24 +699,7 @@ class HipCallbacks:
         qs = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
         if qs.ndim != 1 or len(qs) > MAX_QUANTILES or not np.all((qs >= 0.0) & (qs <= 1.0)):
             raise ValueError(f"predictive: quantiles must be at most {MAX_QUANTILES} numbers in [0, 1], got {quantiles!r}")
-        dev = self._device or torch.device("cuda", torch.cuda.current_device())
-
-        def on_device(a):
-            if not isinstance(a, torch.Tensor):
-                a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64))
-            if not a.is_cuda:
-                a = a.to(dev)
-            return a.to(torch.float64).contiguous()
-        x, w = on_device(x), on_device(w)
-        if x.dim() != 2 or x.shape[1] != self.n_dim or x.shape[0] == 0:
-            raise ValueError(f"predictive: expected (n, {self.n_dim}) points with n > 0, got {tuple(x.shape)}")
-        n = x.shape[0]
-        if w.dim() != 1 or w.shape[0] != n or w.device != x.device:
-            raise ValueError(f"predictive: expected ({n},) weights beside the points, got {tuple(w.shape)} on {w.device}")
-        s1, s2, bad = (float(v) for v in torch.stack([w.sum(), (w * w).sum(), (~(torch.isfinite(w) & (w >= 0))).sum().double()]).cpu())
-        if bad or not s1 > 0.0 or not np.isfinite(s1):
-            raise ValueError("predictive: the weights must be finite, >= 0 and have a positive sum")
-        self._on_table_device(x, "predictive")
+        x, w, n, s1, s2 = self._rows_and_weights(x, w, "predictive")
         R, nq = self.n_predict, len(qs)
         pin = self.predict_tile
         tile, slab = predict_tiles(n, R, nq)
@@ -661,6 +714,46 @@ class HipCallbacks:
                     "tphu_predictive")
         res = out.cpu().numpy()
         return {"mean": res[0].copy(), "var": res[1].copy(), "quantiles": res[2:].copy(), "n_rows": n, "ess": s1 * s1 / s2}
+
+    def pointwise(self, x, w):
+        """Pointwise log predictive densities of a term-form source built with pointwise=True, over the (n, n_dim) points x with
+        weights w (n; >= 0, finite, positive sum, not necessarily normalised; torch-ROCm tensors or NumPy arrays).  With a_ir =
+        log_likelihood_term(x_i, r, D) and u_i = w_i / sum w, a dict of NumPy arrays (n_terms,): "lppd" = log sum u exp(a), "mean" =
+        sum u a, "p_waic" = sum u (a - mean)^2, "elpd_waic" = lppd - p_waic, "elpd_loo" = -log sum u exp(-a) (importance-sampling
+        leave-one-out), "ess_loo" = (sum v)^2 / sum v^2 with v = u exp(-a) -- the effective number of rows behind elpd_loo[r]: a small
+        one marks an estimate not to be trusted --; and "n_rows", "ess" = (sum w)^2 / sum w^2, "totals": the sums over r (math.fsum)
+        elpd_waic, p_waic, lppd, elpd_loo, p_loo = lppd - elpd_loo, and elpd_waic_se, elpd_loo_se = sqrt(n_terms x the population
+        variance of the pointwise values).  Nothing of size n x n_terms is formed; only the (6, n_terms) results come to the host
+        (DESIGN.md section 11).  The scratch is one buffer kept on this object, as for predictive()."""
+        import math
+        import torch
+        if not self.pointwise_enabled:
+            raise TempestHipError("HipCallbacks.pointwise: the object was built without pointwise=True (give it, with a source that defines "
+                                  "log_likelihood_term)")
+        x, w, n, s1, s2 = self._rows_and_weights(x, w, "pointwise")
+        R = self.n_terms
+        tile = int(self.pointwise_tile) or pointwise_tiles(n, R)
+        words = pointwise_scratch_words(n, R)
+        if self._wscratch is None or self._wscratch.numel() < words or self._wscratch.device != x.device:
+            self._wscratch = torch.empty(words, dtype=torch.int64, device=x.device)      # kept: no allocation per call
+        out = torch.empty((len(POINTWISE_KEYS), R), dtype=torch.float64, device=x.device)
+        self._check(self.lib.tphu_pointwise(self._stream(x), x.data_ptr(), w.data_ptr(), n, R, out.data_ptr(), self._wscratch.data_ptr(),
+                                            words, tile, *self._data()), "tphu_pointwise")
+        res = {k: v.copy() for k, v in zip(POINTWISE_KEYS, out.cpu().numpy())}
+
+        def total(v):
+            try:
+                return math.fsum(v)
+            except (ValueError, OverflowError):      # +inf beside -inf among the pointwise values: what a plain sum makes of them
+                with np.errstate(invalid="ignore", over="ignore"):
+                    return float(np.sum(v))
+        tot = {k: total(res[k]) for k in ("elpd_waic", "p_waic", "lppd", "elpd_loo")}
+        tot["p_loo"] = tot["lppd"] - tot["elpd_loo"]
+        with np.errstate(invalid="ignore", over="ignore"):
+            for k in ("elpd_waic", "elpd_loo"):
+                tot[k + "_se"] = float(np.sqrt(R * np.var(res[k])))
+        res.update(n_rows=n, ess=s1 * s1 / s2, totals=tot)
+        return res
 
     # ------------------------------------------------------------------------------ fused MCMC step
     def accept(self, kernel_id, beta, u, x, logl, uprime, maha_u, maha_up, assign, K, dof, seed, tick, item0, sums,

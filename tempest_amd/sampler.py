@@ -144,6 +144,13 @@ class Sampler:
         return self._core.compute_predictive(quantiles=quantiles, trim_importance_weights=trim_importance_weights,
                                              ess_trim=ess_trim, bins_trim=bins_trim)
 
+    def pointwise(self, trim_importance_weights: bool = True, ess_trim: float = 0.99, bins_trim: int = 1000) -> dict:
+        """Pointwise log predictive densities of a HipCallbacks term-form source built with pointwise=True, over the weighted rows
+        posterior() returns: {"lppd", "mean", "p_waic", "elpd_waic", "elpd_loo", "ess_loo": (n_terms,), "n_rows", "ess", "totals"},
+        NumPy (HipCallbacks.pointwise).  The rows stay on the device; nothing of size rows x n_terms is formed.  Not available on a
+        sharded run (NotImplementedError)."""
+        return self._core.compute_pointwise(trim_importance_weights=trim_importance_weights, ess_trim=ess_trim, bins_trim=bins_trim)
+
     def evidence(self) -> tuple:
         """(logZ, None): the reference never computes an error estimate (core.py:151,244-247)."""
         return self._core.compute_evidence()

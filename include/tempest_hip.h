@@ -314,6 +314,35 @@ int tph_gather(tph_ctx* ctx, const int64_t* idx_dev, int64_t n_out, double* u_ou
  * only the kept rows cross PCIe, already in the layout Sampler.posterior() returns. */
 int tph_posterior_rows(tph_ctx* ctx, int key, const int64_t* idx_dev, int64_t m, const double* w_dev, double wdiv,
                        double* x_out /*[m][d]*/, double* logl_out /*[m]*/, double* w_out /*[m] or NULL*/);
+/* ---- posterior marginals (csrc/marginals.hip) ---------------------------------------------
+ * Per-column summaries of m weighted ROW-MAJOR rows v (m, c) that stay on the device: W = sum w, u_i = w_i / W (one division),
+ * integer weights k_i = llrint(u_i 2^52); mean_j = sum u_i v_ij and var_j = sum u_i (v_ij - mean_j)^2 (second pass), every sum over
+ * rows in ONE order -- chunks of 64 consecutive rows by the wave's shuffle tree, blocks of 16 chunk sums in chunk order, block sums
+ * in block order, every level from +0.0, no contraction; range_j = [min, max] of the finite v_ij of rows with w_i > 0 ([v - 0.5,
+ * v + 0.5] when they are equal, [0, 1] when there is none) unless range_host gives [c][2]; counts[j][b] = sum of k_i over the rows
+ * whose v_ij falls in bin b = (int64)((v - lo) * inv), inv = bins / (hi - lo) formed on the host, two roundings, v == hi and a
+ * rounded-up b in the last bin, everything else (NaN, +-inf, beyond the range) in outside[j]; the same over pairs of columns with
+ * bins_2d bins each (first index: the pair's first column); quant[q][j] = the smallest v_ij whose cumulative k reaches
+ * ceil(q 2^52) held inside [1, sum k] -- a radix select, always one of the values; NaN (as mean and var) where a NaN has k > 0.
+ * All tables are 64-bit integer sums: no tile, slab or atomic order changes a bit of any output.
+ * tph_marginals_layout(which): 0 chunk (64), 1 block (16), 2 columns at most (128), 3 bins at most (1024), 4 bins_2d at most
+ * (128), 5 quantiles at most (8), 6 words of batch scratch at most (2^23: 64 MiB), 7 entries of tiles_host (TPH_MARGINALS_TILES).
+ * tph_marginals_scratch_words: 8-byte words of scratch a call needs (W, the block sums of w, the bin parameters, the pairs, and for
+ * a batch of columns the block values of the sweeps and the select's bucket tables -- all columns, or as many as the cap holds).
+ * tiles_host (NULL = all automatic; an entry of 0 = automatic): [0] columns per workgroup of the moment sweeps (<= 16), [1] of the
+ * 1-D histogram (<= 8, and tile x (bins + 1) <= 4100), [2] rows per workgroup of the 1-D histogram and the select (a multiple of
+ * 256), [3] columns per workgroup of the select (tile x n_q <= 16), [4] the 2-D table: 1 = global atomics, 2 = in LDS (bins_2d <=
+ * 64), [5] rows per workgroup of the 2-D histogram (a multiple of 256), [6] words of batch scratch at most (<= 2^23).  They decide
+ * time only.  The caller owns scratch_dev and every output; the call synchronises the stream (the range comes to the host). */
+#define TPH_MARGINALS_TILES 7
+int64_t tph_marginals_layout(int which);
+int64_t tph_marginals_scratch_words(int64_t m, int c, int bins, int n_pairs, int bins_2d, int n_q);
+int tph_marginals(tph_ctx* ctx, const double* rows_dev /*[m][c]*/, int64_t m, int c, const double* w_dev /*[m]*/,
+                  const double* range_host /*[c][2] or NULL*/, int bins, const int32_t* pairs_host /*[n_pairs][2]*/, int n_pairs,
+                  int bins_2d, const double* q_host /*[n_q]*/, int n_q, const int32_t* tiles_host /*[TPH_MARGINALS_TILES] or NULL*/,
+                  int64_t* scratch_dev, int64_t scratch_words, double* moments_dev /*[2][c]: mean, var*/, double* range_dev /*[c][2]*/,
+                  double* quant_dev /*[n_q][c]*/, int64_t* counts_dev /*[c][bins]*/, int64_t* outside_dev /*[c]*/,
+                  int64_t* counts2d_dev /*[n_pairs][bins_2d][bins_2d]*/, int64_t* outside2d_dev /*[n_pairs]*/, int64_t* sumk_dev /*[1]*/);
 /* out[i] = a[b[i]]: indices of a resampling drawn over an already compacted selection */
 int tph_index_compose(tph_ctx* ctx, const int64_t* a_dev, const int64_t* b_dev, int64_t m, int64_t* out_dev);
 /* multiplicity of each history row among factor*(*kept_count_dev) multinomial draws from cdf (modes.py:196-201);

@@ -438,6 +438,42 @@ class SamplerCore:
         x_dev, _, w_sel = ctx.posterior_rows(sel, m_sel, w=w_dev, wdiv=wdiv)
         return owner.pointwise(x_dev, w_sel)
 
+    def compute_marginals(self, bins=64, range=None, quantiles=(0.025, 0.16, 0.5, 0.84, 0.975), pairs=None, bins_2d=32, derived=True,
+                          trim_importance_weights=True, ess_trim=0.99, bins_trim=1000):
+        """Marginal means, variances, quantiles and 1-D / 2-D histograms of the parameters -- and, with `derived`, of the derived
+        quantities -- over the rows and weights compute_posterior returns (same selection, on the device): the rows stay there,
+        only per-column arrays and the tables reach the host (HipContext.marginals)."""
+        import torch
+        from .hipcallbacks import HipCallbacks
+        st = self.state
+        if st.comm is not None and st.comm.active:
+            raise NotImplementedError("Sampler.marginals is not available on a sharded run yet: every rank holds a part of the rows, and "
+                                      "folding per-rank minima, maxima, block sums and tables is not built (DESIGN.md section 10)")
+        ctx = st.ctx
+        ctx.use_current_stream()
+        m, s1, _ = st.reweight_eval([1.0])[0]
+        w_dev = ctx.weights(1.0, m, s1)
+        sel, m_sel, wdiv = self._select_rows(w_dev, trim_importance_weights, ess_trim, bins_trim)
+        x_dev, _, w_sel = ctx.posterior_rows(sel, m_sel, w=w_dev, wdiv=wdiv)
+        n_dim, n_derived = x_dev.shape[1], 0
+        fn = self.config.derived if derived else None
+        owner = getattr(self.config.log_likelihood, "__self__", None)
+        if derived and fn is None and isinstance(owner, HipCallbacks) and owner.n_derived > 0:
+            fn = owner.derived
+        if fn is not None:
+            if isinstance(getattr(fn, "__self__", None), HipCallbacks):      # evaluated where the rows are
+                if fn.__self__.device is None:
+                    fn.__self__.device = st.device
+                extra = fn(x_dev)
+            else:                                                            # a host function: its (M, k) block is uploaded
+                extra = torch.from_numpy(self._derived_fn()(x_dev)).to(x_dev.device)
+            extra = extra.to(torch.float64).reshape(x_dev.shape[0], -1)
+            n_derived = extra.shape[1]
+            x_dev = torch.cat([x_dev, extra], dim=1).contiguous()
+        out = ctx.marginals(x_dev, w_sel, bins=bins, range=range, quantiles=quantiles, pairs=pairs, bins_2d=bins_2d)
+        out.update(n_dim=int(n_dim), n_derived=int(n_derived))
+        return out
+
     def _derived_fn(self):
         """rows (M, d) on the device -> the derived quantities as a host (M, k) float64 array, or None without a derived function:
         config.derived, else the `derived` of the HipCallbacks object the likelihood belongs to."""

@@ -388,6 +388,61 @@ class HipContext:
                                               _ptr(x), _ptr(logl), _ptr(wout)), "tph_posterior_rows")
         return x, logl, wout
 
+    # geometry pins of marginals() for the tests: a dict of some of marginals.MARGINAL_TILE_KEYS (None: the library's rule)
+    marginals_tile = None
+    _mscratch = None
+
+    def marginals(self, rows, w, *, bins=64, range=None, quantiles=(0.025, 0.16, 0.5, 0.84, 0.975), pairs=None, bins_2d=32):
+        """Marginal summaries of the columns of `rows` (M, c), c <= 128 (any c: not tied to n_dim), under the weights `w` (M; >= 0,
+        finite, positive sum, not necessarily normalised; torch-ROCm tensors or NumPy arrays), reduced on the device
+        (tph_marginals).  A dict of NumPy arrays: "mean", "var" (c,), "quantiles" (len(quantiles), c), "range"
+        (c, 2), "edges" (c, bins + 1), "counts" (c, bins) int64 -- sums of the integer weights k_i = rint(w_i / W 2^52) --, "mass" =
+        counts 2^-52, "outside" (c,), "pairs" (P, 2), "counts_2d" (P, bins_2d, bins_2d), "outside_2d" (P,), "edges_2d" (c, bins_2d + 1),
+        and "sum_k", "n_rows", "ess" = (sum w)^2 / sum w^2.  The scratch is one buffer kept on this context."""
+        from . import marginals as mg
+        def on_device(a):
+            if not isinstance(a, torch.Tensor):
+                a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64))
+            if not a.is_cuda:
+                a = a.to(self.device)
+            return a.to(torch.float64).contiguous()
+        rows, w = on_device(rows), on_device(w)
+        if rows.dim() != 2 or rows.shape[0] == 0:
+            raise ValueError(f"marginals: expected (M, c) rows with M > 0, got {tuple(rows.shape)}")
+        m, c = int(rows.shape[0]), int(rows.shape[1])
+        p = mg.plan(c, bins, range, quantiles, pairs, bins_2d)
+        if w.dim() != 1 or w.shape[0] != m or w.device != rows.device or rows.device != self.device:
+            raise ValueError(f"marginals: expected ({m},) weights beside the rows on {self.device}, got {tuple(w.shape)} on {w.device}")
+        s1, s2, bad = (float(v) for v in torch.stack([w.sum(), (w * w).sum(), (~(torch.isfinite(w) & (w >= 0))).sum().double()]).cpu())
+        if bad or not s1 > 0.0 or not np.isfinite(s1):
+            raise ValueError("marginals: the weights must be finite, >= 0 and have a positive sum")
+        B, B2, qs, pr, rng = p["bins"], p["bins_2d"], p["quantiles"], p["pairs"], p["range"]
+        nq, npairs = len(qs), len(pr)
+        tiles = np.zeros(len(mg.MARGINAL_TILE_KEYS), dtype=np.int32)
+        for key, val in (self.marginals_tile or {}).items():
+            tiles[mg.MARGINAL_TILE_KEYS.index(key)] = int(val)
+        words = int(self.lib.tph_marginals_scratch_words(m, c, B, npairs, B2, nq))
+        if words < 0:
+            raise _lib.TempestHipError("tph_marginals_scratch_words refused the request")
+        if self._mscratch is None or self._mscratch.numel() < words:
+            self._mscratch = torch.empty(words, dtype=torch.int64, device=self.device)      # kept: no allocation per call
+        self.use_current_stream()
+        moments, rng_dev, quant = self.empty(2, c), self.empty(c, 2), self.empty(max(nq, 1), c)
+        i64 = dict(dtype=torch.int64)
+        counts, outside, sumk = self.empty(c, B, **i64), self.empty(c, **i64), self.empty(1, **i64)
+        counts2, outside2 = self.empty(max(npairs, 1), B2, B2, **i64), self.empty(max(npairs, 1), **i64)
+        check(self.lib.tph_marginals(self._ctx, _ptr(rows), m, c, _ptr(w), _hptr(rng) if rng is not None else None, B,
+                                     _hptr(pr) if npairs else None, npairs, B2, _hptr(qs) if nq else None, nq, _hptr(tiles),
+                                     _ptr(self._mscratch), self._mscratch.numel(), _ptr(moments), _ptr(rng_dev), _ptr(quant),
+                                     _ptr(counts), _ptr(outside), _ptr(counts2), _ptr(outside2), _ptr(sumk)), "tph_marginals")
+        mom, r = moments.cpu().numpy(), rng_dev.cpu().numpy()
+        cnt = counts.cpu().numpy()
+        return {"mean": mom[0].copy(), "var": mom[1].copy(), "quantiles": quant.cpu().numpy()[:nq].copy(), "range": r,
+                "edges": mg.edges(r, B), "counts": cnt, "mass": cnt * 2.0 ** -52, "outside": outside.cpu().numpy(),
+                "pairs": pr.astype(np.int64), "counts_2d": counts2.cpu().numpy()[:npairs].copy(),
+                "outside_2d": outside2.cpu().numpy()[:npairs].copy(), "edges_2d": mg.edges(r, B2),
+                "sum_k": int(sumk.cpu().numpy()[0]), "n_rows": m, "ess": s1 * s1 / s2}
+
     def index_compose(self, a, b):
         out = self.empty(b.numel(), dtype=torch.int64)
         check(self.lib.tph_index_compose(self._ctx, _ptr(a, torch.int64), _ptr(b, torch.int64), b.numel(), _ptr(out)),

@@ -151,6 +151,17 @@ class Sampler:
         sharded run (NotImplementedError)."""
         return self._core.compute_pointwise(trim_importance_weights=trim_importance_weights, ess_trim=ess_trim, bins_trim=bins_trim)
 
+    def marginals(self, bins: int = 64, range=None, quantiles=(0.025, 0.16, 0.5, 0.84, 0.975), pairs=None, bins_2d: int = 32,
+                  derived: bool = True, trim_importance_weights: bool = True, ess_trim: float = 0.99, bins_trim: int = 1000) -> dict:
+        """Marginals of the posterior over the weighted rows posterior() returns, reduced on the device: {"mean", "var": (c,),
+        "quantiles": (len(quantiles), c), "range": (c, 2), "edges", "counts", "mass": (c, bins), "outside", "pairs", "counts_2d":
+        (P, bins_2d, bins_2d), "outside_2d", "edges_2d", "sum_k", "n_rows", "ess", "n_dim", "n_derived"}, NumPy, c = n_dim +
+        n_derived columns (derived=False: the parameters alone).  `range`: (lo, hi) or (c, 2), else the weighted rows' own; `pairs`:
+        None, "all" or index pairs.  Works with every kind of callback; the rows stay on the device (HipContext.marginals,
+        tempest_amd.marginals.hpd_levels for contour heights).  Not available on a sharded run (NotImplementedError)."""
+        return self._core.compute_marginals(bins=bins, range=range, quantiles=quantiles, pairs=pairs, bins_2d=bins_2d, derived=derived,
+                                            trim_importance_weights=trim_importance_weights, ess_trim=ess_trim, bins_trim=bins_trim)
+
     def evidence(self) -> tuple:
         """(logZ, None): the reference never computes an error estimate (core.py:151,244-247)."""
         return self._core.compute_evidence()

@@ -4,11 +4,14 @@ __version__ = "0.1.0"
 
 from .sampler import Sampler
 
-__all__ = ["Sampler", "HipCallbacks"]
+__all__ = ["Sampler", "HipCallbacks", "trace_callbacks"]
 
 
 def __getattr__(name):          # lazy: importing the package must not need hipcc or a GPU
     if name == "HipCallbacks":
         from .hipcallbacks import HipCallbacks
         return HipCallbacks
+    if name == "trace_callbacks":
+        from .trace import trace_callbacks
+        return trace_callbacks
     raise AttributeError(name)

@@ -270,9 +270,10 @@ def plugin_source(source: str, tables=None, term: bool = False, *, derived: bool
     if term and tables is None:
         tables = ()
     # lines of the data / term form / a source with derived() / with predict() / with pointwise=True only: dropped whole otherwise
-    # (//@Q: what predict and pointwise share -- the layout constants, the row loads, the sum of the weights)
+    # (//@Q: what predict and pointwise share -- the layout constants, the row loads, the sum of the weights; //@R: the helpers a
+    # traced source calls, tempest_amd.trace)
     keep = {"//@D": tables is not None, "//@T": term, "//@X": derived, "//@P": predict, "//@W": pointwise,
-            "//@Q": predict or pointwise}
+            "//@Q": predict or pointwise, "//@R": re.search(r"\btphu_tr_(max|min)\s*\(", source) is not None}
     out = []
     for line in text.split("\n"):
         if line[:4] in keep and line[4:5] in ("", " "):

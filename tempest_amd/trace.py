@@ -1,0 +1,980 @@
+"""Vectorised torch callbacks compiled into the fused step by tracing.
+
+    cb = tempest_amd.trace_callbacks(prior_transform, log_likelihood, n_dim)
+    sampler = tempest_amd.Sampler(cb.prior_transform, cb.log_likelihood, n_dim, vectorize=True, ...)
+
+The user's two functions -- (n, d) float64 -> (n, d) and (n, d) -> (n,), written with torch operations -- are run ONCE on a symbolic
+input that records what is done to it.  The record is a small SSA graph of scalar operations per particle (the leading axis is
+the particle axis and stays symbolic, every trailing shape is static); it is written out as the two HIP device functions
+`hipcallbacks.HipCallbacks` compiles into the Metropolis kernel, one statement per node, and the result is an ordinary
+HipCallbacks object.  Hand-written code generation: no Triton, no inductor, no torch.fx.
+
+What the emitted code computes is specified by `replay` (the graph in NumPy float64, node by node): a statement per operation
+and contraction off, so no multiply-add is fused that eager torch's separate kernels would not fuse; sums, products, means,
+maxima and inner products over the column axis run LEFT TO RIGHT IN COLUMN ORDER.  Where one torch-ROCm device kernel does not
+compute the textbook form, the graph records what that kernel computes: `x / c` with a Python number c is x * (1 / c), `c / x` is (1 / x) * c, `mean` is
+sum * (1 / k), `x ** 2` is x * x.  Everything outside the supported list is refused with a TraceError that
+names the operation, the user's source line and what to write instead.
+"""
+import linecache
+import math
+import os
+import struct
+import sys
+
+import numpy as np
+
+from .tools import SQRTEPS
+
+MAX_WIDTH = 64                  # columns of an intermediate: 64 doubles are a quarter of a lane's 512-VGPR budget
+MAX_CONSTANTS = 64 * 64         # elements of captured arrays embedded in the source
+PROBE_ROWS, PROBE_SEED, _PROBE_TAG = 4096, 20240611, 0x7472
+
+_POINT_TO_DATA = ("straight-line code over that many values is the wrong tool: give the observations as "
+                  "HipCallbacks(source, n_dim, data={...}, n_terms=...) and write log_likelihood_term by hand")
+
+
+class TraceError(Exception):
+    """A callback that cannot be traced, or a trace the probe found wrong.  `.source`: the emitted text, where there is one."""
+    source = None
+
+
+def _where():
+    """file:line: text of the innermost frame that is neither this module nor torch: the user's line."""
+    here, f = os.path.abspath(__file__), sys._getframe(1)
+    while f is not None:
+        fn = f.f_code.co_filename
+        if os.path.abspath(fn) != here and (os.sep + "torch" + os.sep) not in fn:
+            return f"{fn}:{f.f_lineno}: {linecache.getline(fn, f.f_lineno).strip()}"
+        f = f.f_back
+    return "<unknown>"
+
+
+def _refuse(op, why, instead):
+    raise TraceError(f"trace_callbacks: {op} cannot be traced: {why}\n  at {_where()}\n  instead: {instead}")
+
+
+# ------------------------------------------------------------------------------------------------------ the graph
+_BINARY = {"add": "+", "sub": "-", "mul": "*", "div": "/"}
+_CALL2 = {"pow": "pow", "max": "tphu_tr_max", "min": "tphu_tr_min"}
+_UNARY = {"abs": "fabs", "sqrt": "sqrt", "rsqrt": "rsqrt", "exp": "exp", "expm1": "expm1", "log": "log", "log1p": "log1p",
+          "sin": "sin", "cos": "cos", "tan": "tan", "tanh": "tanh", "atan": "atan", "erf": "erf", "erfc": "erfc", "lgamma": "lgamma"}
+_COMPARE = {"gt": ">", "lt": "<", "ge": ">=", "le": "<=", "eq": "==", "ne": "!="}
+_BOOL_OPS = set(_COMPARE) | {"and", "or", "not"}
+_UNINIT = -1
+
+
+class Graph:
+    """nodes[i] = (op, operands): "in" (column,), "const" (the double's 64 bits,), else indices of earlier nodes.  outputs: the node
+    of every output value in row-major order of out_shape (the trailing shape: () for one value per particle)."""
+
+    def __init__(self, n_in, name=""):
+        self.n_in, self.name, self.nodes, self._cse = int(n_in), name, [], {}
+        self.outputs, self.out_shape = (), ()
+        self.widest, self.captured = int(n_in), set()          # captured: the nodes of constants that came from captured arrays
+
+    def add(self, op, *args):
+        key = (op,) + args
+        i = self._cse.get(key)
+        if i is None:
+            i = self._cse[key] = len(self.nodes)
+            self.nodes.append(key)
+        return i
+
+    def const(self, v):
+        return self.add("const", struct.unpack("<q", struct.pack("<d", float(v)))[0])
+
+    def is_bool(self, i):
+        return self.nodes[i][0] in _BOOL_OPS
+
+    def value(self, i):
+        return struct.unpack("<d", struct.pack("<q", self.nodes[i][1]))[0]
+
+    def live(self):
+        """The nodes the outputs need, in emission order (dead nodes dropped)."""
+        need, stack = set(), list(self.outputs)
+        while stack:
+            i = stack.pop()
+            if i not in need:
+                need.add(i)
+                if self.nodes[i][0] not in ("in", "const"):
+                    stack.extend(self.nodes[i][1:])
+        return sorted(need)
+
+    def n_ops(self):
+        return sum(1 for i in self.live() if self.nodes[i][0] not in ("in", "const"))
+
+    def constants(self):
+        return [self.value(i) for i in self.live() if self.nodes[i][0] == "const"]
+
+
+def _literal(v):
+    """A double as a C99 hexadecimal floating literal: no decimal round trip can move a bit."""
+    if math.isnan(v):
+        return '__builtin_nan("")'
+    if math.isinf(v):
+        return "__builtin_inf()" if v > 0 else "-__builtin_inf()"
+    return float.hex(v)
+
+
+def emit(graph, signature, inp, store):
+    """One HIP device function for `graph`: `signature` { one statement per live node; store(k, "tN") per output }."""
+    lines = [signature + " {",
+             "  // traced from " + (graph.name or "a torch callback") + ": one operation per statement, contraction off; sums, products and",
+             "  // inner products over the column axis accumulate left to right in column order",
+             "#pragma clang fp contract(off)"]
+    for i in graph.live():
+        op, args = graph.nodes[i][0], graph.nodes[i][1:]
+        t = [f"t{a}" for a in args]
+        kind = "bool" if op in _BOOL_OPS else "double"
+        if op == "in":
+            rhs = f"{inp}[{args[0]}]"
+        elif op == "const":
+            rhs = _literal(graph.value(i))
+        elif op in _BINARY:
+            rhs = f"{t[0]} {_BINARY[op]} {t[1]}"
+        elif op in _CALL2:
+            rhs = f"{_CALL2[op]}({t[0]}, {t[1]})"
+        elif op in _UNARY:
+            rhs = f"{_UNARY[op]}({t[0]})"
+        elif op == "neg":
+            rhs = f"-{t[0]}"
+        elif op in _COMPARE:
+            rhs = f"{t[0]} {_COMPARE[op]} {t[1]}"
+        elif op == "and":
+            rhs = f"{t[0]} && {t[1]}"
+        elif op == "or":
+            rhs = f"{t[0]} || {t[1]}"
+        elif op == "not":
+            rhs = f"!{t[0]}"
+        elif op == "where":
+            rhs = f"{t[0]} ? {t[1]} : {t[2]}"
+        else:                                        # pragma: no cover
+            raise TraceError(f"emit: unknown node {op!r}")
+        lines.append(f"  const {kind} t{i} = {rhs};")
+    lines += ["  " + store(k, f"t{i}") for k, i in enumerate(graph.outputs)]
+    lines.append("}")
+    return "\n".join(lines)
+
+
+def _torch_unary(name):
+    import torch
+    fn = getattr(torch, name)
+    return lambda a: fn(torch.from_numpy(np.ascontiguousarray(a))).numpy()
+
+
+def replay(graph, array):
+    """The graph evaluated in NumPy float64, node by node in emission order, on the (n, n_in) rows of `array`: what the emitted
+    device function computes -- (n,) + graph.out_shape.  erf, erfc and lgamma (which NumPy lacks) come from torch on the CPU."""
+    a = np.ascontiguousarray(array, dtype=np.float64)
+    if a.ndim != 2 or a.shape[1] != graph.n_in:
+        raise ValueError(f"replay: expected (n, {graph.n_in}) rows, got {a.shape}")
+    n, val = a.shape[0], {}
+    un = {"abs": np.abs, "sqrt": np.sqrt, "rsqrt": lambda v: 1.0 / np.sqrt(v), "exp": np.exp, "expm1": np.expm1, "log": np.log,
+          "log1p": np.log1p, "sin": np.sin, "cos": np.cos, "tan": np.tan, "tanh": np.tanh, "atan": np.arctan, "neg": np.negative,
+          "not": np.logical_not}
+    bi = {"add": np.add, "sub": np.subtract, "mul": np.multiply, "div": np.divide, "pow": np.power, "max": np.maximum,
+          "min": np.minimum, "gt": np.greater, "lt": np.less, "ge": np.greater_equal, "le": np.less_equal, "eq": np.equal,
+          "ne": np.not_equal, "and": np.logical_and, "or": np.logical_or}
+    with np.errstate(all="ignore"):
+        for i in graph.live():
+            op, args = graph.nodes[i][0], graph.nodes[i][1:]
+            if op == "in":
+                val[i] = a[:, args[0]]
+            elif op == "const":
+                val[i] = np.full(n, graph.value(i))
+            elif op in bi:
+                val[i] = bi[op](val[args[0]], val[args[1]])
+            elif op in un:
+                val[i] = un[op](val[args[0]])
+            elif op in ("erf", "erfc", "lgamma"):
+                val[i] = _torch_unary(op)(val[args[0]])
+            elif op == "where":
+                val[i] = np.where(val[args[0]], val[args[1]], val[args[2]])
+            else:                                    # pragma: no cover
+                raise TraceError(f"replay: unknown node {op!r}")
+    out = np.empty((n, len(graph.outputs)))
+    for k, i in enumerate(graph.outputs):
+        out[:, k] = val[i]
+    return out.reshape((n,) + tuple(graph.out_shape))
+
+
+# ------------------------------------------------------------------------------------------------ the symbolic value
+class _Batch:
+    """x.shape[0]: usable as the leading extent of a reshape, and as nothing else."""
+
+    def _no(self, *a, **k):
+        _refuse("x.shape[0] (the number of particles n)", "the particle axis is symbolic; its extent may not enter the arithmetic, "
+                "a loop or an allocation", "write the function per row: reductions over dim=1, no use of n")
+    __add__ = __radd__ = __sub__ = __rsub__ = __mul__ = __rmul__ = __truediv__ = __rtruediv__ = __floordiv__ = __rfloordiv__ = _no
+    __mod__ = __pow__ = __rpow__ = __neg__ = __index__ = __int__ = __float__ = __bool__ = __lt__ = __le__ = __gt__ = __ge__ = _no
+    __hash__ = None
+
+    def __eq__(self, other):
+        return self._no()
+
+    def __repr__(self):
+        return "n"
+
+
+_BATCH = _Batch()
+
+
+def _is_tensor(v):
+    import torch
+    return isinstance(v, torch.Tensor)
+
+
+class TV:
+    """A traced (n,) + ids.shape float64 (or bool) value: ids holds the graph node of every element of a row.  base: the value this
+    one is a VIEW of in torch (basic indexing, reshape / view, squeeze / unsqueeze) -- the tracer holds a copy of its ids, so a write
+    through the view is refused, and so is the use of a view after its base was assigned to (torch would show the change)."""
+    __array_ufunc__ = None          # ndarray <op> TV defers to TV's reflected method
+    __hash__ = None
+
+    def __init__(self, g, ids, is_input=False, base=None):
+        ids = np.asarray(ids, dtype=np.int64)
+        if ids.size > MAX_WIDTH:
+            _refuse(f"an intermediate of {ids.size} columns", f"at most {MAX_WIDTH} values per particle live in registers", _POINT_TO_DATA)
+        g.widest = max(g.widest, int(ids.size))
+        self.g, self._ids, self.is_input, self._version = g, ids, is_input, 0
+        self._base = None if base is None else (base if base._base is None else base._base)       # the root of a chain of views
+        self._base_version = None if base is None else self._base._version
+
+    @property
+    def ids(self):
+        if self._base is not None and self._base._version != self._base_version:
+            _refuse("use of a view after its base was assigned to", "torch would show the new values through the view; the tracer "
+                    "holds the old ones", "take the view (y[:, j], y.reshape(...)) after the assignment, or .clone() it before")
+        return self._ids
+
+    # ---- what a tensor tells about itself
+    @property
+    def shape(self):
+        return (_BATCH,) + tuple(int(s) for s in self.ids.shape)
+
+    def size(self, dim=None):
+        return self.shape if dim is None else self.shape[dim]
+
+    def dim(self):
+        return 1 + self.ids.ndim
+
+    ndim = property(dim)
+
+    @property
+    def dtype(self):
+        import torch
+        return torch.bool if self._bool() else torch.float64
+
+    @property
+    def device(self):
+        import torch
+        return torch.device("cpu")
+
+    def _bool(self):
+        flat = self.ids.ravel()
+        return flat.size > 0 and all(i >= 0 and self.g.is_bool(int(i)) for i in flat)
+
+    def __len__(self):
+        _BATCH._no()
+
+    def __iter__(self):
+        _refuse("iteration over x", "it walks the particle axis", "index columns: x[:, j]")
+
+    def __bool__(self):
+        _refuse("bool() of a traced value (`if`, `while`, `and`, `or`, `assert` on it)", "data-dependent Python control flow takes one "
+                "branch for all particles", "torch.where(condition, a, b)")
+
+    def _scalar(self, *a, **k):
+        _refuse("float() / int() / .item() / .tolist() / .numpy() of a traced value", "the value exists only on the device, per particle",
+                "keep it a tensor expression")
+    __float__ = __int__ = __index__ = item = tolist = numpy = _scalar
+
+    def __getattr__(self, name):
+        if name.startswith("_"):
+            raise AttributeError(name)
+        _refuse(f"x.{name}", "it is outside the supported operation list", "see the list in DESIGN.md section 11; anything else: a "
+                "hand-written HipCallbacks source")
+
+    # ---- dtype and placement
+    def _dtype_refused(self, what):
+        _refuse(what, "traced callbacks are float64 throughout", "drop the conversion (float32 is out of scope)")
+
+    def double(self):
+        return self
+
+    def float(self):
+        self._dtype_refused("x.float()")
+
+    def half(self):
+        self._dtype_refused("x.half()")
+
+    def bfloat16(self):
+        self._dtype_refused("x.bfloat16()")
+
+    def int(self):
+        self._dtype_refused("x.int()")
+
+    def long(self):
+        self._dtype_refused("x.long()")
+
+    def to(self, *args, **kwargs):
+        import torch
+        for a in list(args) + list(kwargs.values()):
+            if isinstance(a, torch.dtype) and a != torch.float64:
+                self._dtype_refused(f"x.to({a})")
+        return self
+
+    type = to
+
+    def cpu(self):
+        return self
+
+    cuda = contiguous = detach = cpu
+
+    def clone(self, *a, **k):
+        return TV(self.g, self.ids.copy())
+
+    # ---- columns
+    def _key(self, key, what):
+        if not isinstance(key, tuple):
+            key = (key,)
+        if not key or not (key[0] is Ellipsis or (isinstance(key[0], slice) and key[0] == slice(None))):
+            _refuse(f"{what} with first index {key[0] if key else key!r}", "the first index selects particles; it must be the full slice",
+                    "x[:, j], x[:, a:b], x[..., j]")
+        rest = []
+        for k in key[1:]:
+            if isinstance(k, TV):
+                _refuse(f"{what} with a traced index or mask", "which column is read would depend on the data", "torch.where")
+            if _is_tensor(k):
+                k = k.detach().cpu().numpy()
+            if isinstance(k, np.ndarray) and k.dtype == bool or isinstance(k, (list, tuple)) and any(isinstance(e, bool) for e in k):
+                k = np.asarray(k, dtype=bool)
+            rest.append(k)
+        n_idx = sum(1 for k in rest if k is not None and k is not Ellipsis)
+        if n_idx > self.ids.ndim:
+            _refuse(what, f"{n_idx} column indices for a value with {self.ids.ndim} trailing axes: the last would index particles",
+                    "x[:, j]")
+        return (Ellipsis,) + tuple(rest) if key[0] is Ellipsis else tuple(rest)
+
+    def __getitem__(self, key):
+        try:
+            k = self._key(key, "x[...]")
+            basic = all(e is None or e is Ellipsis or isinstance(e, (int, np.integer, slice)) for e in k)    # else torch copies
+            return TV(self.g, self.ids[k], base=self if basic else None)
+        except IndexError as e:
+            _refuse("x[...]", str(e), "an index inside the static trailing shape")
+
+    def __setitem__(self, key, value):
+        if self.is_input:
+            _refuse("x[...] = ... on the input", "in-place change of the callback's input", "y = torch.empty_like(x) (or x.clone()) and "
+                    "assign whole columns of y")
+        if self._base is not None:
+            _refuse("y[...] = ... on a view (a value made by indexing, reshape / view, squeeze / unsqueeze)", "torch writes through to "
+                    + ("the callback's input: an in-place change of it" if self._base.is_input else "the value the view was taken from")
+                    + ", which the tracer holds as a copy", "assign to the base itself: base[:, j] = ..." if not self._base.is_input else
+                    "y = x.clone() (or torch.empty_like(x)) and assign whole columns of y")
+        k = self._key(key, "y[...] = ...")
+        ids = self.ids.copy()
+        try:
+            ids[k] = _lift(self.g, value, ids[k].shape)
+        except (IndexError, ValueError) as e:
+            _refuse("y[...] = ...", str(e), "assign whole columns: y[:, j] = ..., y[:, a:b] = ...")
+        self._ids = ids
+        self._version += 1
+
+    def unsqueeze(self, dim):
+        full = 1 + self.ids.ndim + 1
+        d = dim + full if dim < 0 else dim
+        if d == 0:
+            _refuse("unsqueeze(0)", "the particle axis must stay the leading axis", "unsqueeze(-1)")
+        return TV(self.g, np.expand_dims(self.ids, d - 1), base=self)
+
+    def squeeze(self, dim=None):
+        if dim is None:
+            _refuse("squeeze() without dim", "it would also drop a particle axis of extent 1", "squeeze(-1)")
+        d = self._axis(dim, "squeeze")
+        return TV(self.g, np.squeeze(self.ids, d), base=self) if self.ids.shape[d] == 1 else self
+
+    def reshape(self, *shape):
+        if len(shape) == 1 and isinstance(shape[0], (tuple, list)):
+            shape = tuple(shape[0])
+        if not shape or not (shape[0] is _BATCH or (shape[0] == -1 and -1 not in shape[1:] and
+                                                    int(np.prod(shape[1:], dtype=np.int64)) == self.ids.size)):
+            _refuse(f"reshape{tuple(shape)}", "it must keep the particle axis as the leading axis", "x.reshape(x.shape[0], ...) or "
+                    "x.reshape(-1, k) with k the number of values per particle")
+        try:
+            return TV(self.g, self.ids.reshape(tuple(int(s) for s in shape[1:])), base=self)
+        except ValueError as e:
+            _refuse(f"reshape{tuple(shape)}", str(e), "a shape with as many values per particle")
+
+    view = reshape
+
+    def _axis(self, dim, what):
+        full = 1 + self.ids.ndim
+        if not isinstance(dim, (int, np.integer)) or isinstance(dim, bool) or not -full <= dim < full:
+            _refuse(f"{what}(dim={dim!r})", "not an axis of this value", "dim=1 or dim=-1")
+        d = dim + full if dim < 0 else int(dim)
+        if d == 0:
+            _refuse(f"{what} over dim 0", "the particle axis is symbolic: every particle is computed alone",
+                    "dim=1 / dim=-1 (over the columns)")
+        return d - 1
+
+    # ---- arithmetic
+    def _as_double(self):
+        if not self._bool():
+            return self
+        one, zero = self.g.const(1.0), self.g.const(0.0)
+        return TV(self.g, _map(lambda c: self.g.add("where", c, one, zero), self.ids))
+
+    def __neg__(self):
+        return _unary("neg", self)
+
+    def __pos__(self):
+        return self
+
+    def __abs__(self):
+        return _unary("abs", self)
+
+    def __invert__(self):
+        return _logical_not(self)
+
+    def _inplace(self, *a, **k):
+        _refuse("in-place arithmetic (+=, -=, *=, /=, add_, mul_, ...)", "it would change " +
+                ("the callback's input" if self.is_input else "a value other expressions may share"),
+                "y = x + 1 (a new value); column assignment y[:, j] = ... on an empty_like / clone is supported")
+    __iadd__ = __isub__ = __imul__ = __itruediv__ = __ipow__ = __imatmul__ = _inplace
+    add_ = sub_ = mul_ = div_ = pow_ = clamp_ = exp_ = log_ = neg_ = abs_ = sqrt_ = fill_ = zero_ = copy_ = _inplace
+
+    def __matmul__(self, other):
+        return _matmul(self, other)
+
+    def __rmatmul__(self, other):
+        _refuse("A @ x", "the particle axis of x must stay the leading axis of the result", "x @ A.T")
+
+    def __pow__(self, e):
+        return _pow(self, e)
+
+    def __rpow__(self, b):
+        return _pow(b, self)
+
+    @classmethod
+    def __torch_function__(cls, func, types, args=(), kwargs=None):
+        name = getattr(func, "__name__", str(func))
+        h = _TORCH.get(name)
+        if h is None:
+            _refuse(f"torch.{name}", "it is outside the supported operation list", "see the list in DESIGN.md section 11; anything else: "
+                    "a hand-written HipCallbacks source")
+        return h(*args, **(kwargs or {}))
+
+
+def _map(f, *ids):
+    """f over broadcast id arrays, element by element in row-major order."""
+    bs = np.broadcast_arrays(*ids)
+    out = np.empty(bs[0].shape, dtype=np.int64)
+    flat = out.reshape(-1)
+    its = [b.reshape(-1) for b in bs]
+    for k in range(flat.size):
+        vs = [int(it[k]) for it in its]
+        if min(vs) < 0:
+            _refuse("a column of torch.empty_like(...) that was never assigned", "its value is undefined", "assign every column before use")
+        flat[k] = f(*vs)
+    return out
+
+
+def _graph_of(*vals):
+    for v in vals:
+        if isinstance(v, TV):
+            return v.g
+        if isinstance(v, (list, tuple)):
+            for e in v:
+                if isinstance(e, TV):
+                    return e.g
+    raise TraceError("trace_callbacks: no traced value among the operands")
+
+
+def _lift(g, v, tshape):
+    """The node ids of operand `v` against a traced operand of trailing shape `tshape`: a TV (same rank), a Python number, or a
+    captured float64 constant of shape (), (k,), (1, k) ... aligned to the trailing axes."""
+    if isinstance(v, TV):
+        if v.g is not g:
+            _refuse("an operand traced in another callback", "each callback is traced alone", "compute it inside this function")
+        if v.ids.ndim != len(tshape):
+            _refuse(f"broadcasting (n,{','.join(map(str, v.ids.shape))}) against (n,{','.join(map(str, tshape))})",
+                    "it would align the particle axis with a column axis", "unsqueeze(-1) / x[:, j:j+1] on the narrower operand")
+        return v.ids
+    if isinstance(v, _Batch):
+        v._no()
+    if isinstance(v, (bool, int, float, np.floating, np.integer)):
+        return np.asarray(g.const(float(v)), dtype=np.int64)
+    if _is_tensor(v):
+        import torch
+        if v.dtype != torch.float64 and v.dim() > 0 or v.is_complex():
+            _refuse(f"a captured {v.dtype} tensor", "traced callbacks are float64 throughout", "build the constant with dtype=torch.float64")
+        v = v.detach().to("cpu", torch.float64).numpy()
+    a = np.asarray(v)
+    if a.dtype != np.float64 and a.ndim > 0 or a.dtype == object or a.dtype.kind not in "fiub":
+        _refuse(f"a captured {a.dtype} array", "traced callbacks are float64 throughout", "build the constant with dtype=np.float64")
+    a = a.astype(np.float64)
+    while a.ndim > len(tshape) and a.shape[0] == 1:
+        a = a[0]
+    if a.ndim > len(tshape):
+        _refuse(f"a captured constant of shape {np.asarray(v).shape} against (n,{','.join(map(str, tshape))})",
+                "its leading axis would align with the particle axis", "constants of shape (), (k,) or (1, k)")
+    ids = np.vectorize(g.const, otypes=[np.int64])(a) if a.size else a.astype(np.int64)
+    if a.ndim:
+        g.captured.update(int(i) for i in ids.reshape(-1))         # equal values are one node, however often they are used
+    if len(g.captured) > MAX_CONSTANTS:
+        _refuse(f"more than {MAX_CONSTANTS} embedded constants", "every constant becomes a literal of the kernel", _POINT_TO_DATA)
+    return ids
+
+
+def _operands(*vals):
+    g = _graph_of(*vals)
+    tshape = next(v.ids.shape for v in vals if isinstance(v, TV))
+    for v in vals:                      # the widest traced operand sets the rank
+        if isinstance(v, TV) and v.ids.ndim > len(tshape):
+            tshape = v.ids.shape
+    try:
+        ids = [_lift(g, v, tshape) for v in vals]
+        np.broadcast_shapes(*[i.shape for i in ids])
+    except ValueError as e:
+        _refuse("broadcasting", str(e), "operands whose column axes match or are 1")
+    return g, ids
+
+
+def _dbl(g, v, ids):
+    """Bool operands of arithmetic become 1.0 / 0.0 (torch's type promotion)."""
+    return v._as_double().ids if isinstance(v, TV) and v._bool() else ids
+
+
+def _unary(op, a):
+    a = a._as_double()
+    return TV(a.g, _map(lambda i: a.g.add(op, i), a.ids))
+
+
+def _is_number(v):
+    if isinstance(v, (int, float, np.floating, np.integer)) and not isinstance(v, bool):
+        return True
+    return (_is_tensor(v) or isinstance(v, np.ndarray)) and v.ndim == 0 and (not _is_tensor(v) or not v.is_cuda)
+
+
+def _binary(op, a, b, alpha=1, out=None, **kw):
+    if out is not None or kw.get("rounding_mode") is not None:
+        _refuse(f"torch.{op}(..., out= / rounding_mode=)", "only true elementwise results are traced", "the plain operator")
+    if alpha != 1:
+        b = b * alpha
+    g, (ia, ib) = _operands(a, b)
+    ia, ib = _dbl(g, a, ia), _dbl(g, b, ib)
+    if op == "div" and _is_number(b):
+        # torch-ROCm's device kernel for tensor / host scalar multiplies by the reciprocal
+        inv = g.const(1.0 / float(b)) if float(b) != 0.0 else g.const(math.copysign(math.inf, float(b)))
+        return TV(g, _map(lambda i: g.add("mul", i, inv), ia))
+    return TV(g, _map(lambda i, j: g.add(op, i, j), ia, ib))
+
+
+def _compare(op, a, b):
+    g, (ia, ib) = _operands(a, b)
+    return TV(g, _map(lambda i, j: g.add(op, i, j), _dbl(g, a, ia), _dbl(g, b, ib)))
+
+
+def _need_bool(v, what):
+    if not (isinstance(v, TV) and v._bool()):
+        _refuse(what, "its operands must be results of comparisons", "compare first: (x > 0) & (x < 1)")
+
+
+def _logical(op, a, b):
+    _need_bool(a, f"logical_{op}")
+    _need_bool(b, f"logical_{op}")
+    g, (ia, ib) = _operands(a, b)
+    return TV(g, _map(lambda i, j: g.add(op, i, j), ia, ib))
+
+
+def _logical_not(a):
+    _need_bool(a, "logical_not")
+    return TV(a.g, _map(lambda i: a.g.add("not", i), a.ids))
+
+
+def _where3(c, a=None, b=None):
+    if a is None or b is None:
+        _refuse("torch.where(condition) with one argument", "it returns indices, whose number depends on the data",
+                "torch.where(condition, a, b)")
+    _need_bool(c, "torch.where")
+    g, (ic, ia, ib) = _operands(c, a, b)
+    return TV(g, _map(lambda k, i, j: g.add("where", k, i, j), ic, _dbl(g, a, ia), _dbl(g, b, ib)))
+
+
+def _pow(a, e):
+    """Exponents 2, 3, 0.5, -0.5, -1, -2 as torch's own pow kernel computes them; the rest through the device pow()."""
+    if isinstance(a, TV) and _is_number(e):
+        e = float(e)
+        g = a.g
+        one = g.const(1.0)
+        if e == 0.0:
+            return TV(g, _map(lambda i: one, a.ids))
+        forms = {1.0: lambda i: i, 2.0: lambda i: g.add("mul", i, i), 3.0: lambda i: g.add("mul", g.add("mul", i, i), i),
+                 0.5: lambda i: g.add("sqrt", i), -0.5: lambda i: g.add("rsqrt", i), -1.0: lambda i: g.add("div", one, i),
+                 -2.0: lambda i: g.add("div", one, g.add("mul", i, i))}
+        if e in forms:
+            return TV(g, _map(forms[e], a._as_double().ids))
+    g, (ia, ib) = _operands(a, e)
+    return TV(g, _map(lambda i, j: g.add("pow", i, j), _dbl(g, a, ia), _dbl(g, e, ib)))
+
+
+def _clamp(a, min=None, max=None, **kw):
+    if min is None and max is None:
+        _refuse("clamp() without bounds", "nothing to do", "clamp(min=..., max=...)")
+    if min is not None:
+        a = _binary("max", a, min)
+    if max is not None:
+        a = _binary("min", a, max)
+    return a
+
+
+def _fold(g, op, ids):
+    """ids[0] op ids[1] op ... left to right."""
+    acc = ids[0]
+    for i in ids[1:]:
+        acc = g.add(op, acc, i)
+    return acc
+
+
+def _reduce(kind, a, dim=None, keepdim=False, dtype=None, out=None, **kw):
+    import torch
+    if not isinstance(a, TV):
+        _refuse(f"torch.{kind}", "its first operand is not the traced value", "reduce the traced tensor")
+    if dtype not in (None, torch.float64) or out is not None:
+        _refuse(f"{kind}(dtype= / out=)", "traced callbacks are float64 throughout", "drop the argument")
+    if "axis" in kw:
+        dim = kw.pop("axis")
+    if dim is None or (isinstance(dim, (tuple, list)) and len(dim) == 0):
+        _refuse(f"{kind}() over all axes", "it would reduce over the particles", f"{kind}(dim=1)")
+    a = a._as_double()
+    g = a.g
+    dims = sorted({a._axis(d, kind) for d in (dim if isinstance(dim, (tuple, list)) else (dim,))})
+    if a.ids.size == 0 or any(a.ids.shape[d] == 0 for d in dims):
+        _refuse(f"{kind} over no columns", "empty reduction", "reduce at least one column")
+    rest = [d for d in range(a.ids.ndim) if d not in dims]
+    moved = np.transpose(a.ids, rest + dims)
+    lead = moved.shape[:len(rest)]
+    rows = moved.reshape(int(np.prod(lead, dtype=np.int64)), -1)          # the reduced columns of an output, in column order
+    if (rows < 0).any():
+        _map(lambda i: i, rows)                                           # refuses the unassigned column
+    k = rows.shape[1]
+
+    def one(ids):
+        ids = [int(i) for i in ids]
+        if kind in ("sum", "mean"):
+            s = _fold(g, "add", ids)
+            return s if kind == "sum" else g.add("mul", s, g.const(1.0 / k))      # the device mean kernel scales by 1 / k
+        if kind == "prod":
+            return _fold(g, "mul", ids)
+        if kind in ("amax", "amin"):
+            return _fold(g, kind[1:], ids)
+        # logsumexp as torch composes it: m = amax, 0 where |m| is infinite; log(sum exp(x - m)) + m
+        m = _fold(g, "max", ids)
+        m0 = g.add("where", g.add("eq", g.add("abs", m), g.const(math.inf)), g.const(0.0), m)
+        return g.add("add", g.add("log", _fold(g, "add", [g.add("exp", g.add("sub", i, m0)) for i in ids])), m0)
+    res = np.array([one(r) for r in rows], dtype=np.int64).reshape(lead)
+    if keepdim:
+        for d in dims:
+            res = np.expand_dims(res, d)
+    return TV(g, res)
+
+
+def _const_matrix(g, A, what):
+    if isinstance(A, TV):
+        _refuse(what, "both operands are traced", "the second operand must be a captured constant matrix; an inner product of two "
+                "traced rows is (a * b).sum(dim=1)")
+    ids = _lift(g, A, (0, 0))
+    if ids.ndim != 2:
+        _refuse(what, f"the constant has shape {ids.shape}", "a 2-D float64 constant")
+    return ids
+
+
+def _matmul(x, A, transposed=False):
+    """x (n, k) @ A (k, m): out[:, j] = ((x0 * A0j + x1 * A1j) + x2 * A2j) + ... -- products and sums in index order."""
+    if not isinstance(x, TV):
+        _refuse("A @ x", "the particle axis of x must stay the leading axis of the result", "x @ A.T")
+    x = x._as_double()
+    g = x.g
+    if x.ids.ndim != 1:
+        _refuse("matmul", f"the traced operand must be (n, k), got (n,{','.join(map(str, x.ids.shape))})", "reshape to (n, k) first")
+    a = _const_matrix(g, A, "matmul")
+    if transposed:
+        a = a.T
+    if a.shape[0] != x.ids.shape[0]:
+        _refuse("matmul", f"(n, {x.ids.shape[0]}) @ {a.shape}", "matching inner extents")
+    _map(lambda i: i, x.ids)
+    out = [_fold(g, "add", [g.add("mul", int(x.ids[i]), int(a[i, j])) for i in range(a.shape[0])]) for j in range(a.shape[1])]
+    return TV(g, out)
+
+
+def _linear(x, weight, bias=None):
+    y = _matmul(x, weight, transposed=True)
+    return y if bias is None else _binary("add", y, bias)
+
+
+def _seq(tensors, what):
+    if not isinstance(tensors, (list, tuple)) or not tensors:
+        _refuse(what, "expected a list of tensors", f"{what}([a, b, ...], dim=1)")
+    g = _graph_of(tensors)
+    ref = next(t for t in tensors if isinstance(t, TV))
+    return g, [_lift(g, t, ref.ids.shape) if not isinstance(t, TV) else t._as_double().ids if t._bool() else t.ids for t in tensors]
+
+
+def _stack(tensors, dim=0, out=None):
+    g, ids = _seq(tensors, "torch.stack")
+    full = 2 + ids[0].ndim
+    d = dim + full if dim < 0 else dim
+    if d == 0 or not 0 <= d < full:
+        _refuse(f"torch.stack(dim={dim})", "the particle axis must stay the leading axis", "torch.stack([...], dim=1) or dim=-1")
+    try:
+        return TV(g, np.stack([np.broadcast_to(i, ids[0].shape) if i.ndim == 0 else i for i in ids], axis=d - 1))
+    except ValueError as e:
+        _refuse("torch.stack", str(e), "operands of one shape")
+
+
+def _cat(tensors, dim=0, out=None, **kw):
+    dim = kw.get("axis", dim)
+    g, ids = _seq(tensors, "torch.cat")
+    full = 1 + ids[0].ndim
+    d = dim + full if dim < 0 else dim
+    if d == 0 or not 0 <= d < full:
+        _refuse(f"torch.cat(dim={dim})", "it would join along the particle axis", "torch.cat([...], dim=1) or dim=-1")
+    try:
+        return TV(g, np.concatenate(ids, axis=d - 1))
+    except ValueError as e:
+        _refuse("torch.cat", str(e), "operands that agree in the other axes")
+
+
+def _like(fill):
+    def make(a, dtype=None, **kw):
+        import torch
+        if dtype not in (None, torch.float64):
+            a._dtype_refused(f"*_like(dtype={dtype})")
+        ids = np.full(a.ids.shape, _UNINIT if fill is None else a.g.const(fill), dtype=np.int64)
+        return TV(a.g, ids)
+    return make
+
+
+def _method(name):
+    return lambda self, *a, **k: _TORCH[name](self, *a, **k)
+
+
+def _sigmoid(a):
+    # torch's device kernel: 1 / (1 + exp(-x))
+    return _binary("div", 1.0, _binary("add", 1.0, _unary("exp", _unary("neg", a))))
+
+
+_TORCH = {
+    "neg": lambda a: _unary("neg", a), "negative": lambda a: _unary("neg", a), "abs": lambda a: _unary("abs", a),
+    "absolute": lambda a: _unary("abs", a), "square": lambda a: _pow(a, 2.0), "reciprocal": lambda a: _pow(a, -1.0),
+    "sigmoid": _sigmoid, "minimum": lambda a, b: _binary("min", a, b), "maximum": lambda a, b: _binary("max", a, b),
+    "clamp": _clamp, "clip": _clamp, "where": _where3, "pow": _pow, "matmul": _matmul, "linear": _linear,
+    "logical_and": lambda a, b: _logical("and", a, b), "logical_or": lambda a, b: _logical("or", a, b), "logical_not": _logical_not,
+    "stack": _stack, "cat": _cat, "concat": _cat, "concatenate": _cat,
+    "empty_like": _like(None), "zeros_like": _like(0.0), "ones_like": _like(1.0),
+    "clone": lambda a, **k: a.clone(), "unsqueeze": lambda a, dim: a.unsqueeze(dim), "squeeze": lambda a, dim=None: a.squeeze(dim),
+    "reshape": lambda a, *s: a.reshape(*s),
+    "__rpow__": lambda a, b: _pow(b, a), "__pow__": _pow, "__matmul__": _matmul,
+    "__rmatmul__": lambda a, b: _matmul(b, a),
+}
+for _n in _UNARY:
+    if _n != "abs":
+        _TORCH[_n] = (lambda op: lambda a: _unary(op, a))(_n)
+_TORCH["arctan"] = _TORCH["atan"]
+for _n, _alts in (("add", ("__add__", "__radd__")), ("mul", ("multiply", "__mul__", "__rmul__")), ("sub", ("subtract", "__sub__")),
+                  ("div", ("divide", "true_divide", "__truediv__"))):
+    for _a in (_n,) + _alts:
+        _TORCH[_a] = (lambda op: lambda a, b, **k: _binary(op, a, b, **k))(_n)
+_TORCH["__rsub__"] = _TORCH["rsub"] = lambda a, b, **k: _binary("sub", b, a, **k)
+
+
+
+def _rdiv(a, b):
+    """number / x through the operator: torch's Tensor.__rtruediv__ is x.reciprocal() * number, two roundings, on the host and on the
+    device (torch.div(c, x) with a 0-d tensor c, and tensor / x, are true divisions)."""
+    return _binary("mul", _pow(a, -1.0), b) if isinstance(a, TV) and _is_number(b) and not (_is_tensor(b) or isinstance(b, np.ndarray)) \
+        else _binary("div", b, a)
+
+
+_TORCH["__rtruediv__"] = _TORCH["__rdiv__"] = _rdiv
+for _n in _COMPARE:
+    for _a in (_n, f"__{_n}__") + {"gt": ("greater",), "lt": ("less",), "ge": ("greater_equal",), "le": ("less_equal",),
+                                   "eq": (), "ne": ("not_equal",)}[_n]:
+        _TORCH[_a] = (lambda op: lambda a, b: _compare(op, a, b))(_n)
+for _n in ("sum", "mean", "prod", "amax", "amin", "logsumexp"):
+    _TORCH[_n] = (lambda kind: lambda a, *args, **k: _reduce(kind, a, *args, **k))(_n)
+_TORCH["__and__"] = _TORCH["bitwise_and"] = _TORCH["logical_and"]
+_TORCH["__or__"] = _TORCH["bitwise_or"] = _TORCH["logical_or"]
+_TORCH["__invert__"] = _TORCH["bitwise_not"] = _TORCH["logical_not"]
+
+# the methods of a traced value: the same handlers
+for _n in ("neg", "negative", "abs", "absolute", "square", "reciprocal", "sigmoid", "minimum", "maximum", "clamp", "clip", "where", "pow",
+           "matmul", "logical_and", "logical_or", "logical_not", "add", "sub", "mul", "div", "subtract", "multiply", "divide",
+           "true_divide", "sum", "mean", "prod", "amax", "amin", "logsumexp", "arctan", "gt", "lt", "ge", "le", "eq", "ne") \
+        + tuple(n for n in _UNARY if n != "abs"):
+    setattr(TV, _n, _method(_n))
+for _n in ("add", "mul", "sub", "truediv", "rsub", "rtruediv", "gt", "lt", "ge", "le", "eq", "ne", "and", "or"):
+    setattr(TV, f"__{_n}__", _method(f"__{_n}__"))
+TV.__radd__ = lambda self, o: _binary("add", o, self)
+TV.__rmul__ = lambda self, o: _binary("mul", o, self)
+TV.__rand__ = lambda self, o: _logical("and", o, self)
+TV.__ror__ = lambda self, o: _logical("or", o, self)
+
+
+# ------------------------------------------------------------------------------------------------------ tracing
+def trace_function(fn, n_in, out_width=None, name=None):
+    """Run `fn` once on a symbolic (n, n_in) float64 input; returns its Graph.  out_width: an int -> (n, out_width) expected, () ->
+    (n,) expected, None -> (n, k) or (n,) as it comes."""
+    if not callable(fn):
+        raise TypeError(f"trace_callbacks: expected a callable, got {type(fn).__name__}")
+    g = Graph(n_in, name or getattr(fn, "__name__", "callback"))
+    x = TV(g, [g.add("in", j) for j in range(n_in)], is_input=True)
+    y = fn(x)
+    if not isinstance(y, TV):
+        raise TraceError(f"trace_callbacks: {g.name} returned {type(y).__name__}, not a value computed from its input with the "
+                         "supported torch operations")
+    y = y._as_double()
+    if y.ids.ndim > 1 or (out_width is not None and y.ids.shape != ((out_width,) if out_width != () else ())):
+        want = "(n, k) or (n,)" if out_width is None else f"(n, {out_width})" if out_width != () else "(n,)"
+        raise TraceError(f"trace_callbacks: {g.name} returned (n,{','.join(map(str, y.ids.shape))}), expected {want}"
+                         + (" (squeeze(-1) a trailing axis of extent 1)" if out_width == () else ""))
+    _map(lambda i: i, y.ids)                        # every output column assigned
+    g.outputs, g.out_shape = tuple(int(i) for i in y.ids.reshape(-1)), tuple(y.ids.shape)
+    return g
+
+
+def emit_source(graphs):
+    """The HipCallbacks source for {"prior_transform": Graph, "log_likelihood": Graph[, "derived": Graph]}."""
+    parts = ["// emitted by tempest_amd.trace_callbacks (DESIGN.md section 11): values live in registers, one statement per graph node"]
+    parts.append(emit(graphs["prior_transform"], "__device__ void prior_transform(const double* u, double* x)", "u",
+                      lambda k, t: f"x[{k}] = {t};"))
+    parts.append(emit(graphs["log_likelihood"], "__device__ double log_likelihood(const double* x)", "x", lambda k, t: f"return {t};"))
+    if "derived" in graphs:
+        parts.append(emit(graphs["derived"], "__device__ void derived(const double* x, double* out)", "x",
+                          lambda k, t: f"out[{k}] = {t};"))
+    return "\n".join(parts) + "\n"
+
+
+def probe_batch(n_dim, rows=PROBE_ROWS, seed=PROBE_SEED):
+    """(rows, n_dim) uniforms of the package's Philox host twin: item = row, draw = column."""
+    from ._philox_host import philox4x32
+    item, draw = np.meshgrid(np.arange(rows, dtype=np.uint64), np.arange(n_dim, dtype=np.uint64), indexing="ij")
+    zero = np.zeros_like(item)
+    r = philox4x32(item, draw, zero, zero + np.uint64(_PROBE_TAG), seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
+    k = ((r[0] >> np.uint64(5)) << np.uint64(26)) | (r[1] >> np.uint64(6))
+    return k.astype(np.float64) * 2.0 ** -53
+
+
+def _ulps(a, b):
+    def key(v):
+        i = np.ascontiguousarray(v, dtype=np.float64).view(np.int64)
+        return np.where(i < 0, np.int64(-2 ** 63) - i, i)
+    ka, kb = key(a), key(b)
+    far = (ka < 0) != (kb < 0)
+    with np.errstate(over="ignore"):
+        d = np.abs(ka - kb).astype(np.float64)
+    return np.where(far, np.abs(ka.astype(np.float64) - kb.astype(np.float64)), d)
+
+
+def compare(eager, traced):
+    """(largest |difference|, largest difference in ulps, non-finite patterns agree, within SQRTEPS (1 + |eager|)) of two arrays."""
+    e, t = np.asarray(eager, dtype=np.float64), np.asarray(traced, dtype=np.float64)
+    if e.shape != t.shape:
+        return math.inf, math.inf, False, False
+    same = bool(np.array_equal(np.isnan(e), np.isnan(t)) and np.array_equal(np.isposinf(e), np.isposinf(t))
+                and np.array_equal(np.isneginf(e), np.isneginf(t)))
+    fin = np.isfinite(e) & np.isfinite(t)
+    if not fin.any():
+        return 0.0, 0.0, same, True
+    d = np.abs(e[fin] - t[fin])
+    return float(d.max()), float(_ulps(e[fin], t[fin]).max()), same, bool(np.all(d <= SQRTEPS * (1.0 + np.abs(e[fin]))))
+
+
+def probe(cb, prior_transform, log_likelihood, derived=None):
+    """Compare the eager callables with the compiled plugin `cb` (with a device) or with the replay of its graphs (without) on the
+    probe batch; returns the report, raises TraceError (with .source) where they disagree."""
+    import torch
+    graphs, d = cb.trace_graphs, cb.n_dim
+    u = probe_batch(d)
+    on_device = torch.cuda.is_available()
+    report = {"rows": PROBE_ROWS, "seed": PROBE_SEED, "against": "compiled plugin on the device" if on_device else
+              "replay on the CPU (no device present: the compiled code was NOT run)"}
+
+    report["eager_on"] = {}
+
+    def eager(name, fn, a):
+        t = torch.from_numpy(a)
+        if on_device:
+            try:
+                report["eager_on"][name] = "device"
+                return fn(t.to(cb.device or "cuda")).detach().cpu().numpy()
+            except RuntimeError as e:   # constants captured on the host, and that alone: the eager side is evaluated there
+                if "Expected all tensors to be on the same device" not in str(e):
+                    raise
+        report["eager_on"][name] = "cpu"
+        return torch.as_tensor(fn(t)).detach().cpu().numpy()
+
+    def traced(name, a):
+        if on_device:
+            return np.asarray(getattr(cb, name)(a))
+        return replay(graphs[name], a)
+    x = eager("prior_transform", prior_transform, u)
+    pairs = [("prior_transform", x, traced("prior_transform", u))]
+    if x.shape == u.shape:
+        pairs.append(("log_likelihood", eager("log_likelihood", log_likelihood, x), traced("log_likelihood", x)))
+        if derived is not None:
+            e = eager("derived", derived, x)
+            pairs.append(("derived", e, traced("derived", x).reshape(e.shape) if e.size == x.shape[0] * cb.n_derived else None))
+    bad = []
+    for name, e, t in pairs:
+        mx, ul, same, ok = compare(e, t) if t is not None else (math.inf, math.inf, False, False)
+        report[name] = {"max_abs_diff": mx, "max_ulps": ul, "nonfinite_agree": same}
+        if not same:
+            bad.append(f"{name}: the non-finite values (NaN, +inf, -inf) fall on other rows than the eager function's")
+        elif not ok:
+            bad.append(f"{name}: differs from the eager function by up to {mx:.3g} ({ul:.3g} ulp), beyond SQRTEPS (1 + |eager|)")
+    if bad:
+        err = TraceError("trace_callbacks: the probe found the traced code wrong on " + report["against"] + ":\n  " + "\n  ".join(bad)
+                         + "\n  (a function whose Python control flow depends on values the tracer cannot see? the emitted text is in "
+                         "this error's .source)")
+        err.source, err.report = cb.source, report
+        raise err
+    return report
+
+
+def trace_callbacks(prior_transform, log_likelihood, n_dim, derived=None, check=True, **hipcallbacks_kwargs):
+    """The user's vectorised torch callbacks -- (n, d) float64 -> (n, d) and (n, d) -> (n,), unchanged -- as a HipCallbacks object:
+    traced, emitted as HIP device functions, compiled by the usual HipCallbacks constructor.  derived: (n, d) -> (n, k) or (n,),
+    becomes the source's derived(); check: run the probe (see `probe`).  cb.source holds the emitted text, cb.trace_report the op
+    counts, the widest intermediate, the embedded constants and the probe's figures, cb.trace_graphs the graphs (for `replay`)."""
+    from .hipcallbacks import HipCallbacks
+    if not isinstance(n_dim, (int, np.integer)) or isinstance(n_dim, bool) or n_dim <= 0:
+        raise ValueError(f"n_dim must be a positive int, got {n_dim!r}")
+    n_dim = int(n_dim)
+    for k in ("data", "n_terms", "n_predict", "pointwise", "n_derived"):
+        if hipcallbacks_kwargs.get(k):
+            raise ValueError(f"trace_callbacks: {k}= belongs to hand-written sources (the data / term / predict forms are not traced)")
+    if n_dim > MAX_WIDTH:
+        raise TraceError(f"trace_callbacks: n_dim = {n_dim} is wider than {MAX_WIDTH} columns; {_POINT_TO_DATA}")
+    graphs = {"prior_transform": trace_function(prior_transform, n_dim, n_dim, "prior_transform"),
+              "log_likelihood": trace_function(log_likelihood, n_dim, (), "log_likelihood")}
+    if derived is not None:
+        graphs["derived"] = trace_function(derived, n_dim, None, "derived")
+    source = emit_source(graphs)
+    n_derived = max(1, len(graphs["derived"].outputs)) if derived is not None else None
+    try:
+        cb = HipCallbacks(source, n_dim, n_derived=n_derived, **hipcallbacks_kwargs)
+    except Exception as e:
+        e.source = source
+        raise
+    cb.trace_graphs = graphs
+    cb.trace_report = {"ops": {k: g.n_ops() for k, g in graphs.items()}, "n_ops": sum(g.n_ops() for g in graphs.values()),
+                       "widest": max(g.widest for g in graphs.values()),
+                       "constants": sorted({float.hex(c) if math.isfinite(c) else repr(c) for g in graphs.values() for c in g.constants()}),
+                       "probe": None}
+    if check:
+        cb.trace_report["probe"] = probe(cb, prior_transform, log_likelihood, derived)
+    return cb

@@ -435,7 +435,7 @@ int tph_cluster_counts(tph_ctx* ctx, const int32_t* assign_dev, int64_t n, int K
 int tph_fit_modes(tph_ctx* ctx, const int32_t* counts_dev, const int32_t* labels_dev, int64_t n, int K,
                   double* means_dev, double* covs_dev, double* chol_dev, double* inv_dev, double* cholinv_dev /*or NULL*/);
 /* Cholesky L, inverse Sigma^-1 = L^-T L^-1 and (cholinv_dev, optional) L^-1 of K d x d matrices with the reference's
- * ridge rule (modes.py:105-119) */
+ * ridge rule (modes.py:105-119).  n_dim <= 143: one workgroup per matrix holds the factor in the LDS of its CU. */
 int tph_chol_inv(tph_ctx* ctx, double* covs_dev, int K, double* chol_dev, double* inv_dev, double* cholinv_dev /*or NULL*/);
 
 /* ---- volume variation (tools.py:58-117) ---------------------------------------------------------

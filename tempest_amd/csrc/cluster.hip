@@ -427,10 +427,19 @@ static int em_mstep(tph_ctx* ctx, const double* x_dev, int64_t ld, int64_t n, in
   return 0;
 }
 
+// Largest n_dim of the device-paced loop.  k_em_params alone would take 101 (two d x d copies and its 16 static bytes in the 160 KB
+// of a CU: 16 * 101^2 + 16 = 163 232 B), but every iteration ends in the M-step, whose covariance kernel (modes.hip, COV_NPT)
+// holds d (d + 1) / 2 <= 5 120 pairs: n_dim <= 100.  (A limit of 101 here let 101-D through to be refused by the M-step, behind
+// kernels already enqueued.)
+constexpr int EM_MAX_DIM = 100;
+static_assert(sizeof(double) * 2 * EM_MAX_DIM * EM_MAX_DIM + 16 <= 160 * 1024, "k_em_params: factor and inverse must fit a CU's LDS");
+static_assert(EM_MAX_DIM * (EM_MAX_DIM + 1) / 2 <= 20 * 256, "M-step: pairs of the covariance kernel");
+
 // the fit's first M-step (from the initial responsibilities in wr) and a fresh control block
 extern "C" int tph_gmm_em_begin(tph_ctx* ctx, const double* x_dev, int64_t ld, int64_t n, int K, const double* wr_dev,
                                 double* state_dev) {
   TPH_REQUIRE(ctx && x_dev && wr_dev && state_dev && n > 0 && ld >= n && K >= 1 && K <= GMM_KMAX_RESP, "tph_gmm_em_begin: bad argument");
+  TPH_REQUIRE(ctx->d <= EM_MAX_DIM, "tph_gmm_em_begin: n_dim=%d > %d", ctx->d, EM_MAX_DIM);
   const em_layout L = em_lay(ctx->d, K);
   hipLaunchKernelGGL(k_em_begin, dim3(1), dim3(64), 0, ctx->stream, state_dev + L.ctl);
   if (int rc = em_mstep(ctx, x_dev, ld, n, K, wr_dev, state_dev, L)) return rc;
@@ -447,7 +456,7 @@ extern "C" int tph_gmm_em_run(tph_ctx* ctx, const double* x_dev, int64_t ld, int
   const int d = ctx->d;
   const em_layout L = em_lay(d, K);
   const size_t lds = sizeof(double) * 2 * (size_t)d * d;
-  TPH_REQUIRE(lds <= 160 * 1024, "tph_gmm_em_run: n_dim=%d too large", d);
+  TPH_REQUIRE(d <= EM_MAX_DIM, "tph_gmm_em_run: n_dim=%d > %d", d, EM_MAX_DIM);
   if (lds > 64 * 1024)
     TPH_HIP(hipFuncSetAttribute((const void*)k_em_params, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   double* ctl = state_dev + L.ctl;

@@ -1386,6 +1386,13 @@ __global__ void __launch_bounds__(256) k_chol_inv(double* __restrict__ covs, int
 
 extern "C" int tph_chol_inv(tph_ctx* ctx, double* covs_dev, int K, double* chol_dev, double* inv_dev, double* cholinv_dev) {
   TPH_REQUIRE(ctx && covs_dev && chol_dev && inv_dev && K >= 1, "tph_chol_inv: bad argument");
+  // The factor always lives in LDS (its inverse too while both fit 150 KB, see w_lds below): one d x d copy beside the kernel's
+  // static words (fail, piv: 16 bytes) must fit the 160 KB of a CU, i.e. n_dim <= 143.  Stated here, before anything is allocated
+  // or launched, instead of as whatever the launch of an oversized workgroup reports.
+  constexpr size_t lds_cu = 160 * 1024, lds_static = 16;
+  TPH_REQUIRE(sizeof(double) * (size_t)ctx->d * ctx->d + lds_static <= lds_cu,
+              "tph_chol_inv: n_dim=%d too large: one %d x %d factor (%zu B) beside %zu static bytes exceeds the %zu B of LDS of a CU "
+              "(n_dim <= 143)", ctx->d, ctx->d, ctx->d, sizeof(double) * (size_t)ctx->d * ctx->d, lds_static, lds_cu);
   double* work = cholinv_dev;            // W = L^-1: an output when asked for, scratch otherwise
   if (!work) {
     size_t need = sizeof(double) * (size_t)K * ctx->d * ctx->d;
@@ -2288,6 +2295,8 @@ static int vv_reduce(tph_ctx* ctx, const vv_canon& c, const double* partials, in
 extern "C" int tph_volume_variation(tph_ctx* ctx, const double* w_dev, int64_t n, double* centre_dev, double* value_host) {
   TPH_REQUIRE(ctx && w_dev && value_host && n > 0 && n <= ctx->size, "tph_volume_variation: bad argument");
   const int d = ctx->d;
+  // (the covariance kernel's limit, COV_NPT; it also keeps k_vv_prepare inside a CU's LDS: two 97 x 97 copies or one 100 x 100
+  // copy beside its 3 096 static bytes are below 160 KB)
   TPH_REQUIRE(d <= 100, "tph_volume_variation: n_dim=%d > 100", d);
   const bool comm = ctx->comm_active();
   // persistent small buffers behind small_dev: s0 | mean[d] | flag[2] | s | then d x d matrices in the winv-style block

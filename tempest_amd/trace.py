@@ -15,6 +15,11 @@ maxima and inner products over the column axis run LEFT TO RIGHT IN COLUMN ORDER
 compute the textbook form, the graph records what that kernel computes: `x / c` with a Python number c is x * (1 / c), `c / x` is (1 / x) * c, `mean` is
 sum * (1 / k), `x ** 2` is x * x.  Everything outside the supported list is refused with a TraceError that
 names the operation, the user's source line and what to write instead.
+
+Likelihoods over observed data (`data=`, `n_terms=`, `predict=`): the callbacks take the entries as a second argument D; the term
+function (x, D) -> (n, n_terms) returns one column per observation and is emitted as `log_likelihood_term(x, r, D)`, the column at
+the term index r -- the library owns the sum.  Under the tracer an entry has no particle axis: one as long as the term axis is a
+value per term (`D.t[r]`), so is a column of a 2-D entry and `xs @ D["X"].T`; constant integer indices read one element.
 """
 import linecache
 import math
@@ -31,7 +36,12 @@ MAX_CONSTANTS = 64 * 64         # elements of captured arrays embedded in the so
 PROBE_ROWS, PROBE_SEED, _PROBE_TAG = 4096, 20240611, 0x7472
 
 _POINT_TO_DATA = ("straight-line code over that many values is the wrong tool: give the observations as "
-                  "HipCallbacks(source, n_dim, data={...}, n_terms=...) and write log_likelihood_term by hand")
+                  "HipCallbacks(source, n_dim, data={...}, n_terms=...) and write log_likelihood_term by hand, or as "
+                  "trace_callbacks(..., data={...}, n_terms=...) with a term function of (x, D)")
+_OWNS_THE_SUM = "the library owns the sum over observations"
+_NO_TERM_AXIS = ("this callback (prior_transform, derived, a log_likelihood without n_terms=) has no term axis: only the term "
+                 "function (n_terms=) and predict (n_predict=) return one column per observation")
+_RETURN_TERMS = "return the (n, n_terms) terms; reduce over the other axes (dim=1) only"
 
 
 class TraceError(Exception):
@@ -50,8 +60,26 @@ def _where():
     return "<unknown>"
 
 
-def _refuse(op, why, instead):
-    raise TraceError(f"trace_callbacks: {op} cannot be traced: {why}\n  at {_where()}\n  instead: {instead}")
+def _refuse(op, why, instead, at=None):
+    raise TraceError(f"trace_callbacks: {op} cannot be traced: {why}\n  at {at or _where()}\n  instead: {instead}")
+
+
+def _call(fn, *args):
+    """fn(*args); a torch function that rejects the symbolic extent of an axis by its type (torch.arange(n_terms)) before the extent
+    could refuse the use itself is refused here, at the user's line of the traceback."""
+    try:
+        return fn(*args)
+    except TypeError as e:
+        kinds = [k for k in (_TermExtent, _Batch) if k.__name__ in str(e)]
+        if not kinds:
+            raise
+        here, at, tb = os.path.abspath(__file__), None, e.__traceback__
+        while tb is not None:
+            fn_ = tb.tb_frame.f_code.co_filename
+            if os.path.abspath(fn_) != here and (os.sep + "torch" + os.sep) not in fn_:
+                at = f"{fn_}:{tb.tb_lineno}: {linecache.getline(fn_, tb.tb_lineno).strip()}"
+            tb = tb.tb_next
+        _refuse(*kinds[0]._WHY, at=at)
 
 
 # ------------------------------------------------------------------------------------------------------ the graph
@@ -61,17 +89,24 @@ _UNARY = {"abs": "fabs", "sqrt": "sqrt", "rsqrt": "rsqrt", "exp": "exp", "expm1"
           "sin": "sin", "cos": "cos", "tan": "tan", "tanh": "tanh", "atan": "atan", "erf": "erf", "erfc": "erfc", "lgamma": "lgamma"}
 _COMPARE = {"gt": ">", "lt": "<", "ge": ">=", "le": "<=", "eq": "==", "ne": "!="}
 _BOOL_OPS = set(_COMPARE) | {"and", "or", "not"}
+_LEAF = ("in", "const", "dterm", "delem")         # nodes without operand nodes: what follows the op are plain ints
 _UNINIT = -1
 
 
 class Graph:
-    """nodes[i] = (op, operands): "in" (column,), "const" (the double's 64 bits,), else indices of earlier nodes.  outputs: the node
-    of every output value in row-major order of out_shape (the trailing shape: () for one value per particle)."""
+    """nodes[i] = (op, operands): "in" (column,), "const" (the double's 64 bits,), "dterm" (table, column) -- the data entry at
+    position `table` of the spec read at the term index r: D.name[r], or D.name[r * D.name_cols + column] (column -1: a 1-D entry)
+    --, "delem" (table, i, j) -- the element D.name[i] (j = -1) or D.name[i * D.name_cols + j] --, else indices of earlier nodes.
+    outputs: the node of every output value in row-major order of out_shape (the trailing shape: () for one value per particle).
+    tables: ((name, rank), ...) of the data entries; n_term: the extent of the term axis (None: a callback without one), term_name
+    its name ("n_terms" / "n_predict"); reads: {entry: {how it is read}}."""
 
-    def __init__(self, n_in, name=""):
+    def __init__(self, n_in, name="", tables=None, n_term=None, term_name="n_terms"):
         self.n_in, self.name, self.nodes, self._cse = int(n_in), name, [], {}
         self.outputs, self.out_shape = (), ()
         self.widest, self.captured = int(n_in), set()          # captured: the nodes of constants that came from captured arrays
+        self.tables, self.n_term, self.reads = tables, n_term, {}
+        self.term_extent = _TermExtent(term_name)
 
     def add(self, op, *args):
         key = (op,) + args
@@ -97,12 +132,12 @@ class Graph:
             i = stack.pop()
             if i not in need:
                 need.add(i)
-                if self.nodes[i][0] not in ("in", "const"):
+                if self.nodes[i][0] not in _LEAF:
                     stack.extend(self.nodes[i][1:])
         return sorted(need)
 
     def n_ops(self):
-        return sum(1 for i in self.live() if self.nodes[i][0] not in ("in", "const"))
+        return sum(1 for i in self.live() if self.nodes[i][0] not in _LEAF)
 
     def constants(self):
         return [self.value(i) for i in self.live() if self.nodes[i][0] == "const"]
@@ -117,8 +152,17 @@ def _literal(v):
     return float.hex(v)
 
 
-def emit(graph, signature, inp, store):
-    """One HIP device function for `graph`: `signature` { one statement per live node; store(k, "tN") per output }."""
+def _data_read(graph, op, args, r="r"):
+    """The C expression of a "dterm" / "delem" node."""
+    name = graph.tables[args[0]][0]
+    if op == "dterm":
+        return f"D.{name}[{r}]" if args[1] < 0 else f"D.{name}[{r} * D.{name}_cols + {args[1]}]"
+    return f"D.{name}[{args[1]}]" if args[2] < 0 else f"D.{name}[{args[1]} * D.{name}_cols + {args[2]}]"
+
+
+def emit(graph, signature, inp, store, r="r"):
+    """One HIP device function for `graph`: `signature` { one statement per live node; store(k, "tN") per output }.  r: the name of
+    the term index in the signature (graphs that read data entries per term)."""
     lines = [signature + " {",
              "  // traced from " + (graph.name or "a torch callback") + ": one operation per statement, contraction off; sums, products and",
              "  // inner products over the column axis accumulate left to right in column order",
@@ -131,6 +175,8 @@ def emit(graph, signature, inp, store):
             rhs = f"{inp}[{args[0]}]"
         elif op == "const":
             rhs = _literal(graph.value(i))
+        elif op in ("dterm", "delem"):
+            rhs = _data_read(graph, op, args, r)
         elif op in _BINARY:
             rhs = f"{t[0]} {_BINARY[op]} {t[1]}"
         elif op in _CALL2:
@@ -163,16 +209,29 @@ def _torch_unary(name):
     return lambda a: fn(torch.from_numpy(np.ascontiguousarray(a))).numpy()
 
 
-def replay(graph, array):
+def replay(graph, array, data=None):
     """The graph evaluated in NumPy float64, node by node in emission order, on the (n, n_in) rows of `array`: what the emitted
-    device function computes -- (n,) + graph.out_shape.  erf, erfc and lgamma (which NumPy lacks) come from torch on the CPU."""
+    device function computes -- (n,) + graph.out_shape; (n, T) for a term or predict graph, whose nodes are evaluated for every
+    (row, term index) -- the device function is called once per pair.  data: {name: array} for graphs that read data entries.
+    exp, log and the other transcendentals, erf, erfc and lgamma come from torch on the CPU."""
     a = np.ascontiguousarray(array, dtype=np.float64)
     if a.ndim != 2 or a.shape[1] != graph.n_in:
         raise ValueError(f"replay: expected (n, {graph.n_in}) rows, got {a.shape}")
     n, val = a.shape[0], {}
-    un = {"abs": np.abs, "sqrt": np.sqrt, "rsqrt": lambda v: 1.0 / np.sqrt(v), "exp": np.exp, "expm1": np.expm1, "log": np.log,
-          "log1p": np.log1p, "sin": np.sin, "cos": np.cos, "tan": np.tan, "tanh": np.tanh, "atan": np.arctan, "neg": np.negative,
-          "not": np.logical_not}
+    per_term, tabs = graph.n_term is not None, None
+    if per_term or any(graph.nodes[i][0] in ("dterm", "delem") for i in graph.live()):
+        if data is None:
+            raise ValueError("replay: this graph reads data entries: give data={name: array}")
+        tabs = [np.ascontiguousarray(data[name], dtype=np.float64) for name, _ in graph.tables]
+        for t, (name, rank) in zip(tabs, graph.tables):
+            if t.ndim != rank:
+                raise ValueError(f"replay: data[{name!r}] has {t.ndim} axes, traced with {rank}")
+    # a per-term graph: every value is (n, 1), (1, T) or (n, T) -- a column of x, a data entry at every r, what is computed from both
+    col = (lambda v: v[:, None]) if per_term else (lambda v: v)
+    # the transcendentals come from torch on the CPU, the library the eager function calls there: NumPy's differ from it by an ulp
+    # on some hosts, and the replay of a trace is held against eager torch to the bit
+    un = {"abs": np.abs, "sqrt": np.sqrt, "rsqrt": lambda v: 1.0 / np.sqrt(v), "neg": np.negative, "not": np.logical_not}
+    un.update({k: _torch_unary(k) for k in ("exp", "expm1", "log", "log1p", "sin", "cos", "tan", "tanh", "atan")})
     bi = {"add": np.add, "sub": np.subtract, "mul": np.multiply, "div": np.divide, "pow": np.power, "max": np.maximum,
           "min": np.minimum, "gt": np.greater, "lt": np.less, "ge": np.greater_equal, "le": np.less_equal, "eq": np.equal,
           "ne": np.not_equal, "and": np.logical_and, "or": np.logical_or}
@@ -180,9 +239,16 @@ def replay(graph, array):
         for i in graph.live():
             op, args = graph.nodes[i][0], graph.nodes[i][1:]
             if op == "in":
-                val[i] = a[:, args[0]]
+                val[i] = col(a[:, args[0]])
             elif op == "const":
-                val[i] = np.full(n, graph.value(i))
+                val[i] = col(np.full(n, graph.value(i)))
+            elif op == "delem":
+                val[i] = col(np.full(n, tabs[args[0]][args[1]] if args[2] < 0 else tabs[args[0]][args[1], args[2]]))
+            elif op == "dterm":
+                t = tabs[args[0]]
+                if not per_term or t.shape[0] != graph.n_term:
+                    raise ValueError(f"replay: data[{graph.tables[args[0]][0]!r}] has {t.shape[0]} rows, traced with {graph.n_term}")
+                val[i] = (t if args[1] < 0 else np.ascontiguousarray(t[:, args[1]]))[None, :]
             elif op in bi:
                 val[i] = bi[op](val[args[0]], val[args[1]])
             elif op in un:
@@ -193,6 +259,8 @@ def replay(graph, array):
                 val[i] = np.where(val[args[0]], val[args[1]], val[args[2]])
             else:                                    # pragma: no cover
                 raise TraceError(f"replay: unknown node {op!r}")
+    if per_term:
+        return np.array(np.broadcast_to(val[graph.outputs[0]], (n, graph.n_term)), dtype=np.float64)
     out = np.empty((n, len(graph.outputs)))
     for k, i in enumerate(graph.outputs):
         out[:, k] = val[i]
@@ -203,9 +271,11 @@ def replay(graph, array):
 class _Batch:
     """x.shape[0]: usable as the leading extent of a reshape, and as nothing else."""
 
+    _WHY = ("x.shape[0] (the number of particles n)", "the particle axis is symbolic; its extent may not enter the arithmetic, "
+            "a loop or an allocation", "write the function per row: reductions over dim=1, no use of n")
+
     def _no(self, *a, **k):
-        _refuse("x.shape[0] (the number of particles n)", "the particle axis is symbolic; its extent may not enter the arithmetic, "
-                "a loop or an allocation", "write the function per row: reductions over dim=1, no use of n")
+        _refuse(*self._WHY)
     __add__ = __radd__ = __sub__ = __rsub__ = __mul__ = __rmul__ = __truediv__ = __rtruediv__ = __floordiv__ = __rfloordiv__ = _no
     __mod__ = __pow__ = __rpow__ = __neg__ = __index__ = __int__ = __float__ = __bool__ = __lt__ = __le__ = __gt__ = __ge__ = _no
     __hash__ = None
@@ -220,6 +290,20 @@ class _Batch:
 _BATCH = _Batch()
 
 
+class _TermExtent(_Batch):
+    """The extent of the term axis (D["t"].shape[0], y.shape[-1]): a name in .shape, and nothing else."""
+    _WHY = ("the extent of the term axis (D[...].shape[0], len(D[...]), range / torch.arange over it)", "the term axis is symbolic, "
+            "like the particle axis: the emitted function computes ONE term, at the index r the library hands it; the term index "
+            "cannot be manufactured", "write the function for all terms at once, (x, D) -> (n, n_terms); an index-dependent value "
+            "goes into a data entry: put it into a data entry (data={'i': np.arange(T, dtype=np.float64)})")
+
+    def __init__(self, name):
+        self._name = name
+
+    def __repr__(self):
+        return self._name
+
+
 def _is_tensor(v):
     import torch
     return isinstance(v, torch.Tensor)
@@ -232,8 +316,11 @@ class TV:
     __array_ufunc__ = None          # ndarray <op> TV defers to TV's reflected method
     __hash__ = None
 
-    def __init__(self, g, ids, is_input=False, base=None):
+    def __init__(self, g, ids, is_input=False, base=None, term=False, batch=True):
+        # term: a last axis over the observations follows the axes of ids (symbolic, like the particle axis: every node is then a
+        # value per (particle, term)); batch False: a data value, without the particle axis
         ids = np.asarray(ids, dtype=np.int64)
+        self.term, self.batch = bool(term), bool(batch)
         if ids.size > MAX_WIDTH:
             _refuse(f"an intermediate of {ids.size} columns", f"at most {MAX_WIDTH} values per particle live in registers", _POINT_TO_DATA)
         g.widest = max(g.widest, int(ids.size))
@@ -248,16 +335,20 @@ class TV:
                     "holds the old ones", "take the view (y[:, j], y.reshape(...)) after the assignment, or .clone() it before")
         return self._ids
 
+    def _new(self, ids, **kw):
+        """A value of this one's kind (term axis, particle axis) with other nodes."""
+        return TV(self.g, ids, term=self.term, batch=self.batch, **kw)
+
     # ---- what a tensor tells about itself
     @property
     def shape(self):
-        return (_BATCH,) + tuple(int(s) for s in self.ids.shape)
+        return ((_BATCH,) if self.batch else ()) + tuple(int(s) for s in self.ids.shape) + ((self.g.term_extent,) if self.term else ())
 
     def size(self, dim=None):
         return self.shape if dim is None else self.shape[dim]
 
     def dim(self):
-        return 1 + self.ids.ndim
+        return int(self.batch) + self.ids.ndim + int(self.term)
 
     ndim = property(dim)
 
@@ -276,7 +367,7 @@ class TV:
         return flat.size > 0 and all(i >= 0 and self.g.is_bool(int(i)) for i in flat)
 
     def __len__(self):
-        _BATCH._no()
+        (_BATCH if self.batch else self.g.term_extent)._no()
 
     def __iter__(self):
         _refuse("iteration over x", "it walks the particle axis", "index columns: x[:, j]")
@@ -333,7 +424,7 @@ class TV:
     cuda = contiguous = detach = cpu
 
     def clone(self, *a, **k):
-        return TV(self.g, self.ids.copy())
+        return self._new(self.ids.copy())
 
     # ---- columns
     def _key(self, key, what):
@@ -352,20 +443,35 @@ class TV:
                 k = np.asarray(k, dtype=bool)
             rest.append(k)
         n_idx = sum(1 for k in rest if k is not None and k is not Ellipsis)
+        # a value with a term axis: an index behind the static axes, or the last one of a key with `...`, meets the term axis
+        if self.term and rest and (n_idx > self.ids.ndim or key[0] is Ellipsis or any(k is Ellipsis for k in rest)):
+            if not (isinstance(rest[-1], slice) and rest[-1] == slice(None)):
+                _refuse(f"{what}: an index, slice, mask or new axis at the term axis", _OWNS_THE_SUM + "; every term is computed alone, "
+                        "and the term axis stays the last one", _RETURN_TERMS)
+            rest, n_idx = rest[:-1], n_idx - 1
         if n_idx > self.ids.ndim:
             _refuse(what, f"{n_idx} column indices for a value with {self.ids.ndim} trailing axes: the last would index particles",
                     "x[:, j]")
         return (Ellipsis,) + tuple(rest) if key[0] is Ellipsis else tuple(rest)
 
     def __getitem__(self, key):
+        if not self.batch:              # a data value: (T,) -> (1, T) aligns as (T,) does; anything else would index the observations
+            ks = key if isinstance(key, tuple) else (key,)
+            if all(k is None or k is Ellipsis or (isinstance(k, slice) and k == slice(None)) for k in ks):
+                return self
+            _refuse("an index, slice or mask into a data value", _OWNS_THE_SUM + " and hands the function one observation at a time",
+                    "D[name][j] with constant integers on the entry itself (an element), or " + _RETURN_TERMS)
         try:
             k = self._key(key, "x[...]")
             basic = all(e is None or e is Ellipsis or isinstance(e, (int, np.integer, slice)) for e in k)    # else torch copies
-            return TV(self.g, self.ids[k], base=self if basic else None)
+            return self._new(self.ids[k], base=self if basic else None)
         except IndexError as e:
             _refuse("x[...]", str(e), "an index inside the static trailing shape")
 
     def __setitem__(self, key, value):
+        if self.term or not self.batch:
+            _refuse("y[...] = ... on a value with a term axis", "column assignment is traced for per-particle values only",
+                    "build the value with torch.stack / torch.where")
         if self.is_input:
             _refuse("x[...] = ... on the input", "in-place change of the callback's input", "y = torch.empty_like(x) (or x.clone()) and "
                     "assign whole columns of y")
@@ -384,21 +490,30 @@ class TV:
         self._version += 1
 
     def unsqueeze(self, dim):
-        full = 1 + self.ids.ndim + 1
+        if not self.batch:
+            if self.ids.ndim == 0 and ((self.term and dim in (0, -2)) or (not self.term and dim in (0, -1))):
+                return self             # (T,) -> (1, T), () -> (1,): aligned against the trailing axes as before
+            _refuse(f"unsqueeze({dim}) of a data value", "the term axis must stay the last axis", "D[name][None, :] or unsqueeze(0)")
+        full = 1 + self.ids.ndim + int(self.term) + 1
         d = dim + full if dim < 0 else dim
         if d == 0:
             _refuse("unsqueeze(0)", "the particle axis must stay the leading axis", "unsqueeze(-1)")
-        return TV(self.g, np.expand_dims(self.ids, d - 1), base=self)
+        if self.term and d == full - 1:
+            _refuse(f"unsqueeze({dim}) behind the term axis", "the term axis must stay the last axis", "unsqueeze(1)")
+        return self._new(np.expand_dims(self.ids, d - 1), base=self)
 
     def squeeze(self, dim=None):
         if dim is None:
             _refuse("squeeze() without dim", "it would also drop a particle axis of extent 1", "squeeze(-1)")
         d = self._axis(dim, "squeeze")
-        return TV(self.g, np.squeeze(self.ids, d), base=self) if self.ids.shape[d] == 1 else self
+        return self._new(np.squeeze(self.ids, d), base=self) if self.ids.shape[d] == 1 else self
 
     def reshape(self, *shape):
         if len(shape) == 1 and isinstance(shape[0], (tuple, list)):
             shape = tuple(shape[0])
+        if self.term or not self.batch:
+            _refuse(f"reshape{tuple(shape)} of a value with a term axis", "the term axis is symbolic and stays the last axis",
+                    "reshape the per-particle operands before they meet the data")
         if not shape or not (shape[0] is _BATCH or (shape[0] == -1 and -1 not in shape[1:] and
                                                     int(np.prod(shape[1:], dtype=np.int64)) == self.ids.size)):
             _refuse(f"reshape{tuple(shape)}", "it must keep the particle axis as the leading axis", "x.reshape(x.shape[0], ...) or "
@@ -411,10 +526,12 @@ class TV:
     view = reshape
 
     def _axis(self, dim, what):
-        full = 1 + self.ids.ndim
+        full = int(self.batch) + self.ids.ndim + int(self.term)
         if not isinstance(dim, (int, np.integer)) or isinstance(dim, bool) or not -full <= dim < full:
             _refuse(f"{what}(dim={dim!r})", "not an axis of this value", "dim=1 or dim=-1")
         d = dim + full if dim < 0 else int(dim)
+        if self.term and d == full - 1:
+            _refuse(f"{what} along the term axis (dim={dim})", _OWNS_THE_SUM, _RETURN_TERMS)
         if d == 0:
             _refuse(f"{what} over dim 0", "the particle axis is symbolic: every particle is computed alone",
                     "dim=1 / dim=-1 (over the columns)")
@@ -425,7 +542,7 @@ class TV:
         if not self._bool():
             return self
         one, zero = self.g.const(1.0), self.g.const(0.0)
-        return TV(self.g, _map(lambda c: self.g.add("where", c, one, zero), self.ids))
+        return self._new(_map(lambda c: self.g.add("where", c, one, zero), self.ids))
 
     def __neg__(self):
         return _unary("neg", self)
@@ -493,16 +610,18 @@ def _graph_of(*vals):
     raise TraceError("trace_callbacks: no traced value among the operands")
 
 
-def _lift(g, v, tshape):
+def _lift(g, v, tshape, term=False, ids=None):
     """The node ids of operand `v` against a traced operand of trailing shape `tshape`: a TV (same rank), a Python number, or a
-    captured float64 constant of shape (), (k,), (1, k) ... aligned to the trailing axes."""
+    captured float64 constant of shape (), (k,), (1, k) ... aligned to the trailing axes.  term: the result has a term axis behind
+    `tshape`; ids: v's nodes less the extent-1 axis that met it (_operands)."""
     if isinstance(v, TV):
         if v.g is not g:
             _refuse("an operand traced in another callback", "each callback is traced alone", "compute it inside this function")
-        if v.ids.ndim != len(tshape):
-            _refuse(f"broadcasting (n,{','.join(map(str, v.ids.shape))}) against (n,{','.join(map(str, tshape))})",
+        ids = v.ids if ids is None else ids
+        if v.batch and ids.ndim != len(tshape):
+            _refuse(f"broadcasting (n,{','.join(map(str, ids.shape))}) against (n,{','.join(map(str, tshape))})",
                     "it would align the particle axis with a column axis", "unsqueeze(-1) / x[:, j:j+1] on the narrower operand")
-        return v.ids
+        return ids
     if isinstance(v, _Batch):
         v._no()
     if isinstance(v, (bool, int, float, np.floating, np.integer)):
@@ -516,6 +635,11 @@ def _lift(g, v, tshape):
     if a.dtype != np.float64 and a.ndim > 0 or a.dtype == object or a.dtype.kind not in "fiub":
         _refuse(f"a captured {a.dtype} array", "traced callbacks are float64 throughout", "build the constant with dtype=np.float64")
     a = a.astype(np.float64)
+    if term and a.ndim:
+        if a.shape[-1] != 1:
+            _refuse(f"a captured array of shape {a.shape} against a value with a term axis", "its last axis would run along the "
+                    "observations", "put it into a data entry (data={...}); constants per column take shape (k, 1)")
+        a = a[..., 0]
     while a.ndim > len(tshape) and a.shape[0] == 1:
         a = a[0]
     if a.ndim > len(tshape):
@@ -530,27 +654,40 @@ def _lift(g, v, tshape):
 
 
 def _operands(*vals):
+    """(graph, the broadcastable node ids of the operands, the kind of the result: term axis, particle axis)."""
     g = _graph_of(*vals)
-    tshape = next(v.ids.shape for v in vals if isinstance(v, TV))
-    for v in vals:                      # the widest traced operand sets the rank
-        if isinstance(v, TV) and v.ids.ndim > len(tshape):
-            tshape = v.ids.shape
+    tvs = [v for v in vals if isinstance(v, TV)]
+    term, batch = any(v.term for v in tvs), any(v.batch for v in tvs)
+
+    def trailing(v):                    # a per-particle operand meets the term axis with a last axis of extent 1, which goes
+        if not (term and v.batch and not v.term):
+            return v.ids
+        if v.ids.ndim == 0 or v.ids.shape[-1] != 1:
+            _refuse(f"broadcasting (n,{','.join(map(str, v.ids.shape))}) against a term axis", "the term axis is the last axis of "
+                    "the other operand: it meets a last axis of extent 1 or another term axis, as torch would align it",
+                    "x[:, j:j+1] or unsqueeze(-1) on the per-particle operand")
+        return v.ids[..., 0]
+    mine = [trailing(v) if isinstance(v, TV) else None for v in vals]
+    tshape = max((i.shape for v, i in zip(vals, mine) if isinstance(v, TV) and v.batch), key=len, default=())
     try:
-        ids = [_lift(g, v, tshape) for v in vals]
+        ids = [_lift(g, v, tshape, term, i) for v, i in zip(vals, mine)]
         np.broadcast_shapes(*[i.shape for i in ids])
     except ValueError as e:
         _refuse("broadcasting", str(e), "operands whose column axes match or are 1")
-    return g, ids
+    return g, ids, {"term": term, "batch": batch}
 
 
 def _dbl(g, v, ids):
     """Bool operands of arithmetic become 1.0 / 0.0 (torch's type promotion)."""
-    return v._as_double().ids if isinstance(v, TV) and v._bool() else ids
+    if isinstance(v, TV) and v._bool():
+        one, zero = g.const(1.0), g.const(0.0)
+        return _map(lambda c: g.add("where", c, one, zero), ids)
+    return ids
 
 
 def _unary(op, a):
     a = a._as_double()
-    return TV(a.g, _map(lambda i: a.g.add(op, i), a.ids))
+    return a._new(_map(lambda i: a.g.add(op, i), a.ids))
 
 
 def _is_number(v):
@@ -564,18 +701,18 @@ def _binary(op, a, b, alpha=1, out=None, **kw):
         _refuse(f"torch.{op}(..., out= / rounding_mode=)", "only true elementwise results are traced", "the plain operator")
     if alpha != 1:
         b = b * alpha
-    g, (ia, ib) = _operands(a, b)
+    g, (ia, ib), kind = _operands(a, b)
     ia, ib = _dbl(g, a, ia), _dbl(g, b, ib)
     if op == "div" and _is_number(b):
         # torch-ROCm's device kernel for tensor / host scalar multiplies by the reciprocal
         inv = g.const(1.0 / float(b)) if float(b) != 0.0 else g.const(math.copysign(math.inf, float(b)))
-        return TV(g, _map(lambda i: g.add("mul", i, inv), ia))
-    return TV(g, _map(lambda i, j: g.add(op, i, j), ia, ib))
+        return TV(g, _map(lambda i: g.add("mul", i, inv), ia), **kind)
+    return TV(g, _map(lambda i, j: g.add(op, i, j), ia, ib), **kind)
 
 
 def _compare(op, a, b):
-    g, (ia, ib) = _operands(a, b)
-    return TV(g, _map(lambda i, j: g.add(op, i, j), _dbl(g, a, ia), _dbl(g, b, ib)))
+    g, (ia, ib), kind = _operands(a, b)
+    return TV(g, _map(lambda i, j: g.add(op, i, j), _dbl(g, a, ia), _dbl(g, b, ib)), **kind)
 
 
 def _need_bool(v, what):
@@ -586,13 +723,13 @@ def _need_bool(v, what):
 def _logical(op, a, b):
     _need_bool(a, f"logical_{op}")
     _need_bool(b, f"logical_{op}")
-    g, (ia, ib) = _operands(a, b)
-    return TV(g, _map(lambda i, j: g.add(op, i, j), ia, ib))
+    g, (ia, ib), kind = _operands(a, b)
+    return TV(g, _map(lambda i, j: g.add(op, i, j), ia, ib), **kind)
 
 
 def _logical_not(a):
     _need_bool(a, "logical_not")
-    return TV(a.g, _map(lambda i: a.g.add("not", i), a.ids))
+    return a._new(_map(lambda i: a.g.add("not", i), a.ids))
 
 
 def _where3(c, a=None, b=None):
@@ -600,8 +737,8 @@ def _where3(c, a=None, b=None):
         _refuse("torch.where(condition) with one argument", "it returns indices, whose number depends on the data",
                 "torch.where(condition, a, b)")
     _need_bool(c, "torch.where")
-    g, (ic, ia, ib) = _operands(c, a, b)
-    return TV(g, _map(lambda k, i, j: g.add("where", k, i, j), ic, _dbl(g, a, ia), _dbl(g, b, ib)))
+    g, (ic, ia, ib), kind = _operands(c, a, b)
+    return TV(g, _map(lambda k, i, j: g.add("where", k, i, j), ic, _dbl(g, a, ia), _dbl(g, b, ib)), **kind)
 
 
 def _pow(a, e):
@@ -611,14 +748,14 @@ def _pow(a, e):
         g = a.g
         one = g.const(1.0)
         if e == 0.0:
-            return TV(g, _map(lambda i: one, a.ids))
+            return a._new(_map(lambda i: one, a.ids))
         forms = {1.0: lambda i: i, 2.0: lambda i: g.add("mul", i, i), 3.0: lambda i: g.add("mul", g.add("mul", i, i), i),
                  0.5: lambda i: g.add("sqrt", i), -0.5: lambda i: g.add("rsqrt", i), -1.0: lambda i: g.add("div", one, i),
                  -2.0: lambda i: g.add("div", one, g.add("mul", i, i))}
         if e in forms:
-            return TV(g, _map(forms[e], a._as_double().ids))
-    g, (ia, ib) = _operands(a, e)
-    return TV(g, _map(lambda i, j: g.add("pow", i, j), _dbl(g, a, ia), _dbl(g, e, ib)))
+            return a._new(_map(forms[e], a._as_double().ids))
+    g, (ia, ib), kind = _operands(a, e)
+    return TV(g, _map(lambda i, j: g.add("pow", i, j), _dbl(g, a, ia), _dbl(g, e, ib)), **kind)
 
 
 def _clamp(a, min=None, max=None, **kw):
@@ -643,6 +780,8 @@ def _reduce(kind, a, dim=None, keepdim=False, dtype=None, out=None, **kw):
     import torch
     if not isinstance(a, TV):
         _refuse(f"torch.{kind}", "its first operand is not the traced value", "reduce the traced tensor")
+    if not a.batch:
+        _refuse(f"{kind} of a data value", _OWNS_THE_SUM + ": a data value has no axis but the observations", _RETURN_TERMS)
     if dtype not in (None, torch.float64) or out is not None:
         _refuse(f"{kind}(dtype= / out=)", "traced callbacks are float64 throughout", "drop the argument")
     if "axis" in kw:
@@ -679,7 +818,14 @@ def _reduce(kind, a, dim=None, keepdim=False, dtype=None, out=None, **kw):
     if keepdim:
         for d in dims:
             res = np.expand_dims(res, d)
-    return TV(g, res)
+    return TV(g, res, term=a.term)
+
+
+def _cumsum(a, dim=None, **kw):
+    if isinstance(a, TV) and (not a.batch or a.term):
+        a._axis(dim if a.batch else -1, "cumsum")            # along the term axis: the library owns that sum
+    _refuse("torch.cumsum", "it is outside the supported operation list", "see the list in DESIGN.md section 11; anything else: a "
+            "hand-written HipCallbacks source")
 
 
 def _const_matrix(g, A, what):
@@ -698,8 +844,13 @@ def _matmul(x, A, transposed=False):
         _refuse("A @ x", "the particle axis of x must stay the leading axis of the result", "x @ A.T")
     x = x._as_double()
     g = x.g
-    if x.ids.ndim != 1:
-        _refuse("matmul", f"the traced operand must be (n, k), got (n,{','.join(map(str, x.ids.shape))})", "reshape to (n, k) first")
+    if x.ids.ndim != 1 or x.term or not x.batch:
+        _refuse("matmul", f"the traced operand must be (n, k), got {tuple(x.shape)}", "reshape to (n, k) first")
+    if isinstance(A, (_Entry, _EntryT)):
+        if isinstance(A, _EntryT) == bool(transposed):
+            _refuse("x @ D[name]", "the rows of a design matrix are the observations: the result would have no term axis",
+                    "x @ D[name].T, or torch.nn.functional.linear(x, D[name])")
+        return (A.entry if isinstance(A, _EntryT) else A)._inner(x)
     a = _const_matrix(g, A, "matmul")
     if transposed:
         a = a.T
@@ -720,30 +871,37 @@ def _seq(tensors, what):
         _refuse(what, "expected a list of tensors", f"{what}([a, b, ...], dim=1)")
     g = _graph_of(tensors)
     ref = next(t for t in tensors if isinstance(t, TV))
-    return g, [_lift(g, t, ref.ids.shape) if not isinstance(t, TV) else t._as_double().ids if t._bool() else t.ids for t in tensors]
+    if any(isinstance(t, TV) and (t.term != ref.term or not t.batch) for t in tensors):
+        _refuse(what + " of values with and without a term axis", "their shapes differ", "broadcast first: a + 0.0 * b")
+    return g, [_lift(g, t, ref.ids.shape, ref.term) if not isinstance(t, TV) else t._as_double().ids if t._bool() else t.ids
+               for t in tensors], ref.term
 
 
 def _stack(tensors, dim=0, out=None):
-    g, ids = _seq(tensors, "torch.stack")
-    full = 2 + ids[0].ndim
+    g, ids, term = _seq(tensors, "torch.stack")
+    full = 2 + ids[0].ndim + int(term)
     d = dim + full if dim < 0 else dim
     if d == 0 or not 0 <= d < full:
         _refuse(f"torch.stack(dim={dim})", "the particle axis must stay the leading axis", "torch.stack([...], dim=1) or dim=-1")
+    if term and d == full - 1:
+        _refuse(f"torch.stack(dim={dim}) behind the term axis", "the term axis must stay the last axis", "torch.stack([...], dim=1)")
     try:
-        return TV(g, np.stack([np.broadcast_to(i, ids[0].shape) if i.ndim == 0 else i for i in ids], axis=d - 1))
+        return TV(g, np.stack([np.broadcast_to(i, ids[0].shape) if i.ndim == 0 else i for i in ids], axis=d - 1), term=term)
     except ValueError as e:
         _refuse("torch.stack", str(e), "operands of one shape")
 
 
 def _cat(tensors, dim=0, out=None, **kw):
     dim = kw.get("axis", dim)
-    g, ids = _seq(tensors, "torch.cat")
-    full = 1 + ids[0].ndim
+    g, ids, term = _seq(tensors, "torch.cat")
+    full = 1 + ids[0].ndim + int(term)
     d = dim + full if dim < 0 else dim
     if d == 0 or not 0 <= d < full:
         _refuse(f"torch.cat(dim={dim})", "it would join along the particle axis", "torch.cat([...], dim=1) or dim=-1")
+    if term and d == full - 1:
+        _refuse(f"torch.cat(dim={dim}) along the term axis", _OWNS_THE_SUM + ": the number of terms is the data's", "torch.cat([...], dim=1)")
     try:
-        return TV(g, np.concatenate(ids, axis=d - 1))
+        return TV(g, np.concatenate(ids, axis=d - 1), term=term)
     except ValueError as e:
         _refuse("torch.cat", str(e), "operands that agree in the other axes")
 
@@ -754,7 +912,7 @@ def _like(fill):
         if dtype not in (None, torch.float64):
             a._dtype_refused(f"*_like(dtype={dtype})")
         ids = np.full(a.ids.shape, _UNINIT if fill is None else a.g.const(fill), dtype=np.int64)
-        return TV(a.g, ids)
+        return a._new(ids)
     return make
 
 
@@ -778,7 +936,7 @@ _TORCH = {
     "clone": lambda a, **k: a.clone(), "unsqueeze": lambda a, dim: a.unsqueeze(dim), "squeeze": lambda a, dim=None: a.squeeze(dim),
     "reshape": lambda a, *s: a.reshape(*s),
     "__rpow__": lambda a, b: _pow(b, a), "__pow__": _pow, "__matmul__": _matmul,
-    "__rmatmul__": lambda a, b: _matmul(b, a),
+    "__rmatmul__": lambda a, b: _matmul(b, a), "cumsum": _cumsum,
 }
 for _n in _UNARY:
     if _n != "abs":
@@ -818,26 +976,190 @@ for _n in ("neg", "negative", "abs", "absolute", "square", "reciprocal", "sigmoi
     setattr(TV, _n, _method(_n))
 for _n in ("add", "mul", "sub", "truediv", "rsub", "rtruediv", "gt", "lt", "ge", "le", "eq", "ne", "and", "or"):
     setattr(TV, f"__{_n}__", _method(f"__{_n}__"))
+TV.cumsum = _method("cumsum")
 TV.__radd__ = lambda self, o: _binary("add", o, self)
 TV.__rmul__ = lambda self, o: _binary("mul", o, self)
 TV.__rand__ = lambda self, o: _logical("and", o, self)
 TV.__ror__ = lambda self, o: _logical("or", o, self)
 
 
+# ------------------------------------------------------------------------------------------------------ data entries
+class _Entry(TV):
+    """D[name] under the tracer: a data entry has no particle axis and its elements are graph nodes.  A 1-D entry whose length is
+    the term extent is a per-term value ("dterm": D.name[r]), so is a column D[name][:, j] of a 2-D entry with that many rows, and
+    x @ D[name].T their inner product with the columns of x; constant integer indices read one element ("delem")."""
+
+    def __init__(self, g, pos, name, shape, is_f64):
+        self.g, self._pos, self._name, self._shape, self._f64 = g, pos, name, tuple(int(v) for v in shape), bool(is_f64)
+        self.is_input, self._version, self._base, self._base_version, self._ids = False, 0, None, None, None
+        self.term, self.batch = True, False
+
+    def _node(self, op, *args, how):
+        if not self._f64:
+            _refuse(f"D[{self._name!r}], given as an integer or float32 array, in arithmetic", "the device table is float64 and the "
+                    "eager function would compute in another type", f"give it as float64 (np.asarray(..., dtype=np.float64)), or "
+                    f"cast it in the function: D[{self._name!r}].double()")
+        self.g.reads.setdefault(self._name, set()).add(how)
+        return self.g.add(op, self._pos, *args)
+
+    def _per_term(self):
+        return self.g.n_term is not None and self._shape[0] == self.g.n_term
+
+    @property
+    def ids(self):
+        if self._ids is None:
+            n = self._name
+            if len(self._shape) == 2:
+                _refuse(f"D[{n!r}], a 2-D entry, used whole", "its rows are observations and its columns are not an axis of the result",
+                        f"a column D[{n!r}][:, j], an element D[{n!r}][i, j], or xs @ D[{n!r}].T")
+            if not self._per_term():
+                _refuse(f"D[{n!r}], a 1-D entry of length {self._shape[0]}, used whole", "only an entry as long as the term axis ("
+                        f"{self.g.term_extent!r} = {self.g.n_term}) is a value per term" if self.g.n_term is not None else _NO_TERM_AXIS,
+                        f"index it: D[{n!r}][j]")
+            self._ids = np.asarray(self._node("dterm", -1, how="per-term"), dtype=np.int64)
+        return self._ids
+
+    @property
+    def shape(self):
+        return tuple(self.g.term_extent if k == 0 and self._per_term() else v for k, v in enumerate(self._shape))
+
+    def dim(self):
+        return len(self._shape)
+
+    ndim = property(dim)
+
+    @property
+    def dtype(self):
+        import torch
+        return torch.float64
+
+    def __len__(self):
+        if self._per_term():
+            self.g.term_extent._no()
+        return self._shape[0]
+
+    def double(self):
+        return self if self._f64 else _Entry(self.g, self._pos, self._name, self._shape, True)
+
+    def to(self, *args, **kwargs):
+        import torch
+        return self.double() if torch.float64 in list(args) + list(kwargs.values()) else TV.to(self, *args, **kwargs)
+
+    def _index(self, k, axis):
+        extent = self._shape[axis]
+        if not -extent <= k < extent:
+            _refuse(f"D[{self._name!r}][...] with index {k}", f"axis {axis} has extent {extent}", "an index inside the entry's shape")
+        return int(k) % extent
+
+    def __getitem__(self, key):
+        n, ks = self._name, key if isinstance(key, tuple) else (key,)
+        whole = slice(None)
+        if any(isinstance(k, TV) or _is_tensor(k) or isinstance(k, (np.ndarray, list)) for k in ks):
+            _refuse(f"D[{n!r}][...] with a traced index, an index array or a mask", "which element is read would depend on the data: "
+                    "a traced index into a table is a gather", "constant integers D[name][j], or a per-term entry prepared on the host")
+        is_int = [isinstance(k, (int, np.integer)) and not isinstance(k, bool) for k in ks]
+        if all(is_int) and len(ks) == len(self._shape):
+            i = self._index(ks[0], 0)
+            j = self._index(ks[1], 1) if len(ks) == 2 else -1
+            return TV(self.g, self._node("delem", i, j, how=f"element [{i}]" if j < 0 else f"element [{i}, {j}]"), batch=False)
+        if len(self._shape) == 1 and all(k is None or k is Ellipsis or (isinstance(k, slice) and k == whole) for k in ks):
+            self.ids
+            return self
+        if len(self._shape) == 2 and len(ks) == 2 and isinstance(ks[0], slice) and ks[0] == whole and is_int[1]:
+            if not self._per_term():
+                _refuse(f"D[{n!r}][:, j]", f"the entry has {self._shape[0]} rows, not one per term" if self.g.n_term is not None else
+                        _NO_TERM_AXIS, f"elements D[{n!r}][i, j]")
+            j = self._index(ks[1], 1)
+            return TV(self.g, self._node("dterm", j, how=f"column {j}"), term=True, batch=False)
+        _refuse(f"D[{n!r}][{', '.join(map(str, ks))}]: an index, slice or mask along the observations", _OWNS_THE_SUM + " and hands "
+                "the function one observation at a time", f"the entry whole, a column D[{n!r}][:, j], or constant integers; "
+                + _RETURN_TERMS)
+
+    def unsqueeze(self, dim):
+        if len(self._shape) == 1:
+            return TV.unsqueeze(self, dim)
+        self.ids
+
+    @property
+    def T(self):
+        return _EntryT(self) if len(self._shape) == 2 else self
+
+    mT = T
+
+    def t(self):
+        return self.T
+
+    def transpose(self, a, b):
+        return self.T if len(self._shape) == 2 and sorted((a % 2, b % 2)) == [0, 1] else self
+
+    def _inner(self, x):
+        """x (n, k) @ D[name].T, the entry (T, k): the per-term inner product, left to right in column order (_fold, as x @ A)."""
+        n = self._name
+        if len(self._shape) != 2 or not self._per_term():
+            _refuse(f"x @ D[{n!r}].T", f"the entry has shape {self._shape}: it needs one row per term", "a 2-D entry (n_terms, k)")
+        k = self._shape[1]
+        if k > MAX_WIDTH or x.ids.shape[0] != k:
+            _refuse(f"x @ D[{n!r}].T", f"(n, {x.ids.shape[0]}) against {k} columns (at most {MAX_WIDTH})", "matching inner extents")
+        _map(lambda i: i, x.ids)
+        g = self.g
+        return TV(g, _fold(g, "add", [g.add("mul", int(x.ids[i]), self._node("dterm", i, how=f"column {i}")) for i in range(k)]), term=True)
+
+
+class _EntryT:
+    """D[name].T of a 2-D entry: the second operand of x @ D[name].T, and nothing else."""
+    __array_ufunc__ = None
+
+    def __init__(self, entry):
+        self.entry = entry
+
+    def __getattr__(self, name):
+        if name.startswith("_"):
+            raise AttributeError(name)
+        _refuse(f"D[{self.entry._name!r}].T.{name}", "the transpose of a design matrix is traced as the operand of a product only",
+                f"xs @ D[{self.entry._name!r}].T")
+
+
+class _Data(dict):
+    def __missing__(self, name):
+        _refuse(f"D[{name!r}]", "no such data entry", f"one of {sorted(self)}")
+
+
+def _wants_data(fn):
+    """prior_transform and derived get D if and only if they accept a second positional parameter."""
+    import inspect
+    try:
+        ps = list(inspect.signature(fn).parameters.values())
+    except (TypeError, ValueError):
+        return False
+    return sum(p.kind in (p.POSITIONAL_ONLY, p.POSITIONAL_OR_KEYWORD) for p in ps) >= 2
+
+
 # ------------------------------------------------------------------------------------------------------ tracing
-def trace_function(fn, n_in, out_width=None, name=None):
+def trace_function(fn, n_in, out_width=None, name=None, data=None, term=None, pass_data=None):
     """Run `fn` once on a symbolic (n, n_in) float64 input; returns its Graph.  out_width: an int -> (n, out_width) expected, () ->
-    (n,) expected, None -> (n, k) or (n,) as it comes."""
+    (n,) expected, None -> (n, k) or (n,) as it comes.  data: (((name, rank), ...), {name: (shape, is float64)}) -- the entries fn may
+    read through its second argument D (pass_data: hand D over; default: whenever data is given); term: (extent, its name) -- fn
+    returns one column per term, (n, extent), and the graph computes the column at the term index r."""
     if not callable(fn):
         raise TypeError(f"trace_callbacks: expected a callable, got {type(fn).__name__}")
-    g = Graph(n_in, name or getattr(fn, "__name__", "callback"))
+    name = name or getattr(fn, "__name__", "callback")
+    g = Graph(n_in, name, *((data[0],) if data is not None else (None,)), *(term or ()))
     x = TV(g, [g.add("in", j) for j in range(n_in)], is_input=True)
-    y = fn(x)
-    if not isinstance(y, TV):
-        raise TraceError(f"trace_callbacks: {g.name} returned {type(y).__name__}, not a value computed from its input with the "
-                         "supported torch operations")
+    if data is not None and (pass_data is None or pass_data):
+        y = _call(fn, x, _Data((nm, _Entry(g, pos, nm, *data[1][nm])) for pos, (nm, _) in enumerate(data[0])))
+    else:
+        y = _call(fn, x)
+    if not isinstance(y, TV) or not y.batch:
+        raise TraceError(f"trace_callbacks: {g.name} returned {'a data value' if isinstance(y, TV) else type(y).__name__}, not a value "
+                         "computed from its input with the supported torch operations")
     y = y._as_double()
-    if y.ids.ndim > 1 or (out_width is not None and y.ids.shape != ((out_width,) if out_width != () else ())):
+    if term is not None:
+        if not y.term or y.ids.ndim:
+            raise TraceError(f"trace_callbacks: {g.name} returned {tuple(y.shape)}, expected (n, {g.term_extent!r}): one column per "
+                             f"term, the result has no term axis of its own" if not y.term else
+                             f"trace_callbacks: {g.name} returned {tuple(y.shape)}, expected (n, {g.term_extent!r}): reduce the other "
+                             "axes (dim=1) first")
+    elif y.ids.ndim > 1 or (out_width is not None and y.ids.shape != ((out_width,) if out_width != () else ())):
         want = "(n, k) or (n,)" if out_width is None else f"(n, {out_width})" if out_width != () else "(n,)"
         raise TraceError(f"trace_callbacks: {g.name} returned (n,{','.join(map(str, y.ids.shape))}), expected {want}"
                          + (" (squeeze(-1) a trailing axis of extent 1)" if out_width == () else ""))
@@ -846,14 +1168,22 @@ def trace_function(fn, n_in, out_width=None, name=None):
     return g
 
 
-def emit_source(graphs):
-    """The HipCallbacks source for {"prior_transform": Graph, "log_likelihood": Graph[, "derived": Graph]}."""
+def emit_source(graphs, tables=None):
+    """The HipCallbacks source for {"prior_transform": Graph, "log_likelihood" | "log_likelihood_term": Graph[, "predict": Graph]
+    [, "derived": Graph]}.  tables: the data entries -- every signature then carries `const tphu_data& D`, as hand-written ones do."""
+    D = "" if tables is None else ", const tphu_data& D"
     parts = ["// emitted by tempest_amd.trace_callbacks (DESIGN.md section 11): values live in registers, one statement per graph node"]
-    parts.append(emit(graphs["prior_transform"], "__device__ void prior_transform(const double* u, double* x)", "u",
+    parts.append(emit(graphs["prior_transform"], f"__device__ void prior_transform(const double* u, double* x{D})", "u",
                       lambda k, t: f"x[{k}] = {t};"))
-    parts.append(emit(graphs["log_likelihood"], "__device__ double log_likelihood(const double* x)", "x", lambda k, t: f"return {t};"))
+    if "log_likelihood_term" in graphs:
+        parts.append(emit(graphs["log_likelihood_term"], f"__device__ double log_likelihood_term(const double* x, int64_t r{D})", "x",
+                          lambda k, t: f"return {t};"))
+    else:
+        parts.append(emit(graphs["log_likelihood"], f"__device__ double log_likelihood(const double* x{D})", "x", lambda k, t: f"return {t};"))
+    if "predict" in graphs:
+        parts.append(emit(graphs["predict"], f"__device__ double predict(const double* x, int64_t r{D})", "x", lambda k, t: f"return {t};"))
     if "derived" in graphs:
-        parts.append(emit(graphs["derived"], "__device__ void derived(const double* x, double* out)", "x",
+        parts.append(emit(graphs["derived"], f"__device__ void derived(const double* x, double* out{D})", "x",
                           lambda k, t: f"out[{k}] = {t};"))
     return "\n".join(parts) + "\n"
 
@@ -893,40 +1223,97 @@ def compare(eager, traced):
     return float(d.max()), float(_ulps(e[fin], t[fin]).max()), same, bool(np.all(d <= SQRTEPS * (1.0 + np.abs(e[fin]))))
 
 
-def probe(cb, prior_transform, log_likelihood, derived=None):
+def _seq_sum_last(a):
+    """The sum along the last axis, sequentially from +0.0 (np.cumsum adds in order)."""
+    return np.cumsum(np.concatenate([np.zeros(a.shape[:-1] + (1,)), a], axis=-1), axis=-1)[..., -1]
+
+
+def layered_sum(terms, chunk, block):
+    """The (n, T) terms summed in the order every term-form kernel follows (hipcallbacks.SUM_LAYOUT): chunks of
+    `chunk` consecutive terms added in order, blocks of `block` consecutive chunk sums added in order, the block sums added in order;
+    every level starts from +0.0."""
+    t = np.asarray(terms, dtype=np.float64)
+    for width in (chunk, block):
+        n, k = t.shape
+        pad = np.zeros((n, -(-k // width) * width))
+        pad[:, :k] = t
+        t = _seq_sum_last(pad.reshape(n, -1, width))
+    return _seq_sum_last(t)
+
+
+def probe(cb, prior_transform, log_likelihood, derived=None, predict=None):
     """Compare the eager callables with the compiled plugin `cb` (with a device) or with the replay of its graphs (without) on the
-    probe batch; returns the report, raises TraceError (with .source) where they disagree."""
+    probe batch; returns the report, raises TraceError (with .source) where they disagree.  With data the eager functions get the
+    float64 tensors the device tables hold; a term function's eager columns are summed by `layered_sum` and held against
+    cb.log_likelihood (the replayed terms summed alike, without a device), in chunks of rows so that nothing larger than 2^22
+    doubles is formed; predict is checked through cb.predictive with one row of weight 1, which returns predict(x, .) exactly."""
     import torch
+    from .hipcallbacks import SUM_LAYOUT
     graphs, d = cb.trace_graphs, cb.n_dim
-    u = probe_batch(d)
+    data = dict(cb._host) if cb.tables is not None else None
+    term = "log_likelihood_term" in graphs
+    widest = max(cb.n_terms if term else 1, cb.n_predict if "predict" in graphs else 1)
+    rows = PROBE_ROWS if widest == 1 and not term else max(1, min(PROBE_ROWS, 2 ** 22 // widest))
+    u = probe_batch(d, rows)
     on_device = torch.cuda.is_available()
-    report = {"rows": PROBE_ROWS, "seed": PROBE_SEED, "against": "compiled plugin on the device" if on_device else
+    report = {"rows": rows, "seed": PROBE_SEED, "against": "compiled plugin on the device" if on_device else
               "replay on the CPU (no device present: the compiled code was NOT run)"}
 
     report["eager_on"] = {}
+    tensors = {}
 
-    def eager(name, fn, a):
+    def D_on(dev):
+        if dev not in tensors:
+            tensors[dev] = {k: torch.from_numpy(v).to(dev) for k, v in data.items()}
+        return tensors[dev]
+
+    def eager(name, fn, a, with_data=False):
         t = torch.from_numpy(a)
         if on_device:
             try:
                 report["eager_on"][name] = "device"
-                return fn(t.to(cb.device or "cuda")).detach().cpu().numpy()
+                dev = cb.device or "cuda"
+                return fn(t.to(dev), *((D_on(dev),) if with_data else ())).detach().cpu().numpy()
             except RuntimeError as e:   # constants captured on the host, and that alone: the eager side is evaluated there
                 if "Expected all tensors to be on the same device" not in str(e):
                     raise
         report["eager_on"][name] = "cpu"
-        return torch.as_tensor(fn(t)).detach().cpu().numpy()
+        return torch.as_tensor(fn(t, *((D_on("cpu"),) if with_data else ()))).detach().cpu().numpy()
 
     def traced(name, a):
         if on_device:
             return np.asarray(getattr(cb, name)(a))
-        return replay(graphs[name], a)
-    x = eager("prior_transform", prior_transform, u)
+        return replay(graphs[name], a, data)
+
+    def chunks(n_cols):
+        step = max(1, 2 ** 22 // max(1, n_cols))
+        return [slice(i, min(rows, i + step)) for i in range(0, rows, step)]
+
+    def summed(terms, n):
+        terms = np.asarray(terms)
+        return layered_sum(terms, *SUM_LAYOUT) if terms.shape == (n, cb.n_terms) else np.full(n, np.nan)      # a wrong shape fails below
+    has = data is not None
+    x = eager("prior_transform", prior_transform, u, has and _wants_data(prior_transform))
     pairs = [("prior_transform", x, traced("prior_transform", u))]
     if x.shape == u.shape:
-        pairs.append(("log_likelihood", eager("log_likelihood", log_likelihood, x), traced("log_likelihood", x)))
+        if term:
+            e = np.concatenate([summed(eager("log_likelihood", log_likelihood, x[c], True), len(x[c])) for c in chunks(cb.n_terms)])
+            t = traced("log_likelihood", x) if on_device else np.concatenate(
+                [layered_sum(replay(graphs["log_likelihood_term"], x[c], data), *SUM_LAYOUT) for c in chunks(cb.n_terms)])
+            pairs.append(("log_likelihood", e, t))
+        else:
+            pairs.append(("log_likelihood", eager("log_likelihood", log_likelihood, x, has), traced("log_likelihood", x)))
+        if predict is not None and "predict" in graphs:
+            if on_device:                                # at most 8 rows, each alone with weight 1: mean = predict exactly
+                xs = x[:8]
+                t = np.stack([cb.predictive(xs[i:i + 1], np.ones(1), quantiles=(0.5,))["mean"] for i in range(len(xs))])
+            else:
+                xs = x
+                t = np.concatenate([replay(graphs["predict"], x[c], data) for c in chunks(cb.n_predict)])
+            e = np.concatenate([eager("predict", predict, xs[c], True) for c in chunks(cb.n_predict) if len(xs[c])])
+            pairs.append(("predict", e, t))
         if derived is not None:
-            e = eager("derived", derived, x)
+            e = eager("derived", derived, x, has and _wants_data(derived))
             pairs.append(("derived", e, traced("derived", x).reshape(e.shape) if e.size == x.shape[0] * cb.n_derived else None))
     bad = []
     for name, e, t in pairs:
@@ -945,28 +1332,79 @@ def probe(cb, prior_transform, log_likelihood, derived=None):
     return report
 
 
-def trace_callbacks(prior_transform, log_likelihood, n_dim, derived=None, check=True, **hipcallbacks_kwargs):
+def _extent(v, what, host):
+    """n_terms / n_predict: the name of a data entry (its length, or its rows), or an int that some entry has as that extent."""
+    if host is None:
+        raise ValueError(f"trace_callbacks: {what}= goes with data= (the term and predict functions read the observations from D)")
+    if isinstance(v, str):
+        if v not in host:
+            raise ValueError(f"trace_callbacks: {what}={v!r} names no data entry")
+        return int(host[v].shape[0])
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) <= 0:
+        raise ValueError(f"trace_callbacks: {what} must be a positive int or the name of a data entry, got {v!r}")
+    if not any(a.shape[0] == int(v) for a in host.values()):
+        raise ValueError(f"trace_callbacks: {what}={int(v)} is the length (or the number of rows) of no data entry: the traced function "
+                         "has nothing to read per term")
+    return int(v)
+
+
+def _is_f64(a):
+    if _is_tensor(a):
+        import torch
+        return a.dtype == torch.float64
+    return np.asarray(a).dtype == np.float64
+
+
+def trace_callbacks(prior_transform, log_likelihood, n_dim, derived=None, check=True, *, data=None, n_terms=None, predict=None,
+                    n_predict=None, pointwise=False, **hipcallbacks_kwargs):
     """The user's vectorised torch callbacks -- (n, d) float64 -> (n, d) and (n, d) -> (n,), unchanged -- as a HipCallbacks object:
     traced, emitted as HIP device functions, compiled by the usual HipCallbacks constructor.  derived: (n, d) -> (n, k) or (n,),
     becomes the source's derived(); check: run the probe (see `probe`).  cb.source holds the emitted text, cb.trace_report the op
-    counts, the widest intermediate, the embedded constants and the probe's figures, cb.trace_graphs the graphs (for `replay`)."""
-    from .hipcallbacks import HipCallbacks
+    counts, the widest intermediate, the embedded constants, the data entries each callback reads and the probe's figures,
+    cb.trace_graphs the graphs (for `replay`).
+
+    data={name: array}, as HipCallbacks takes it: the callbacks get the entries as a dict D of float64 tensors in a second argument
+    (prior_transform and derived only if they accept one).  With n_terms= (the name of an entry, or an int some entry has as its
+    length or rows) the second callable is the TERM function (x, D) -> (n, n_terms), one column per observation, and the library owns
+    the sum; without it, log_likelihood(x, D) -> (n,) may read elements D[name][j] only.  predict= (x, D) -> (n, n_predict) with
+    n_predict= becomes the source's predict() (predict= without data= is refused: every column would have to be spelled out); pointwise=
+    as in HipCallbacks.  A 1-D entry as long as the term axis is a value per term, used whole; a 2-D entry (T, k) gives columns
+    D[name][:, j] and xs @ D[name].T; constant integer indices read an element of any entry."""
+    from .hipcallbacks import HipCallbacks, _table_spec
     if not isinstance(n_dim, (int, np.integer)) or isinstance(n_dim, bool) or n_dim <= 0:
         raise ValueError(f"n_dim must be a positive int, got {n_dim!r}")
     n_dim = int(n_dim)
-    for k in ("data", "n_terms", "n_predict", "pointwise", "n_derived"):
-        if hipcallbacks_kwargs.get(k):
-            raise ValueError(f"trace_callbacks: {k}= belongs to hand-written sources (the data / term / predict forms are not traced)")
+    if hipcallbacks_kwargs.get("n_derived"):
+        raise ValueError("trace_callbacks: n_derived= belongs to hand-written sources (here it is the width of what derived returns)")
     if n_dim > MAX_WIDTH:
         raise TraceError(f"trace_callbacks: n_dim = {n_dim} is wider than {MAX_WIDTH} columns; {_POINT_TO_DATA}")
-    graphs = {"prior_transform": trace_function(prior_transform, n_dim, n_dim, "prior_transform"),
-              "log_likelihood": trace_function(log_likelihood, n_dim, (), "log_likelihood")}
+    tables, host = (None, None) if data is None else _table_spec(data)
+    spec = None if data is None else (tables, {k: (host[k].shape, _is_f64(data[k])) for k, _ in tables})
+    if predict is None and n_predict is not None:
+        raise ValueError("trace_callbacks: n_predict= goes with predict= (a function (x, D) -> (n, n_predict))")
+    if predict is not None and data is None:
+        raise ValueError("trace_callbacks: predict= without data= is not traced (every column would be an expression of its own): "
+                         "give what depends on the index as a data entry and n_predict= its name")
+    if predict is not None and n_predict is None:
+        raise ValueError("trace_callbacks: predict= needs n_predict= (an int, or the name of a data entry)")
+    if pointwise and n_terms is None:
+        raise ValueError("trace_callbacks: pointwise=True goes with n_terms= (a term function)")
+    wants = {"prior_transform": data is not None and _wants_data(prior_transform), "derived": data is not None and _wants_data(derived)}
+    graphs = {"prior_transform": trace_function(prior_transform, n_dim, n_dim, "prior_transform", spec, pass_data=wants["prior_transform"])}
+    if n_terms is not None:
+        graphs["log_likelihood_term"] = trace_function(log_likelihood, n_dim, None, "log_likelihood_term", spec,
+                                                       (_extent(n_terms, "n_terms", host), "n_terms"))
+    else:
+        graphs["log_likelihood"] = trace_function(log_likelihood, n_dim, (), "log_likelihood", spec)
+    if predict is not None:
+        graphs["predict"] = trace_function(predict, n_dim, None, "predict", spec, (_extent(n_predict, "n_predict", host), "n_predict"))
     if derived is not None:
-        graphs["derived"] = trace_function(derived, n_dim, None, "derived")
-    source = emit_source(graphs)
+        graphs["derived"] = trace_function(derived, n_dim, None, "derived", spec, pass_data=wants["derived"])
+    source = emit_source(graphs, tables)
     n_derived = max(1, len(graphs["derived"].outputs)) if derived is not None else None
+    data_kwargs = {} if data is None else {"data": host, "n_terms": n_terms, "n_predict": n_predict, "pointwise": bool(pointwise)}
     try:
-        cb = HipCallbacks(source, n_dim, n_derived=n_derived, **hipcallbacks_kwargs)
+        cb = HipCallbacks(source, n_dim, n_derived=n_derived, **data_kwargs, **hipcallbacks_kwargs)
     except Exception as e:
         e.source = source
         raise
@@ -975,6 +1413,8 @@ def trace_callbacks(prior_transform, log_likelihood, n_dim, derived=None, check=
                        "widest": max(g.widest for g in graphs.values()),
                        "constants": sorted({float.hex(c) if math.isfinite(c) else repr(c) for g in graphs.values() for c in g.constants()}),
                        "probe": None}
+    if data is not None:
+        cb.trace_report["reads"] = {k: {name: sorted(how) for name, how in g.reads.items()} for k, g in graphs.items()}
     if check:
-        cb.trace_report["probe"] = probe(cb, prior_transform, log_likelihood, derived)
+        cb.trace_report["probe"] = probe(cb, prior_transform, log_likelihood, derived, predict)
     return cb

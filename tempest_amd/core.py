@@ -414,6 +414,31 @@ class SamplerCore:
         x_dev, _, w_sel = ctx.posterior_rows(sel, m_sel, w=w_dev, wdiv=wdiv)
         return owner.predictive(x_dev, w_sel, quantiles)
 
+    def compute_replicated(self, quantiles=(0.025, 0.5, 0.975), seed=None, trim_importance_weights=True, ess_trim=0.99, bins_trim=1000):
+        """Replicated-data bands, PIT and Bayesian p-value of the HipCallbacks source's replicate(x, r, g) over the rows and weights
+        compute_posterior returns (same selection and row order, on the device): the rows are gathered and reduced there, only the
+        (n_replicate,) results reach the host.  seed None: the run's seed."""
+        from ._lib import TempestHipError
+        from .hipcallbacks import HipCallbacks
+        owner = getattr(self.config.log_likelihood, "__self__", None)
+        if not isinstance(owner, HipCallbacks) or not owner.n_replicate:
+            raise TempestHipError("Sampler.replicated: the likelihood is no HipCallbacks source that defines replicate(...) (give it and "
+                                  "n_replicate=)")
+        st = self.state
+        if st.comm is not None and st.comm.active:
+            raise NotImplementedError("Sampler.replicated is not available on a sharded run yet: every rank holds a part of the rows, and "
+                                      "a global row index for the draws and folding per-rank sums and counts are not built (DESIGN.md "
+                                      "section 10)")
+        ctx = st.ctx
+        ctx.use_current_stream()
+        if owner.device is None:
+            owner.device = st.device
+        m, s1, _ = st.reweight_eval([1.0])[0]
+        w_dev = ctx.weights(1.0, m, s1)
+        sel, m_sel, wdiv = self._select_rows(w_dev, trim_importance_weights, ess_trim, bins_trim)
+        x_dev, _, w_sel = ctx.posterior_rows(sel, m_sel, w=w_dev, wdiv=wdiv)
+        return owner.replicated(x_dev, w_sel, quantiles, seed=self.rng.seed if seed is None else seed)
+
     def compute_pointwise(self, trim_importance_weights=True, ess_trim=0.99, bins_trim=1000):
         """Pointwise log predictive densities, WAIC and importance-sampling LOO of a pointwise-enabled HipCallbacks source over the
         rows and weights compute_posterior returns (same selection, on the device): the rows are gathered and reduced there, only

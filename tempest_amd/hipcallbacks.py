@@ -105,6 +105,10 @@ PREDICT_SCRATCH_WORDS = 1 << 23    # 64 MiB of batch scratch at most: more indic
 POINTWISE_MAX_TILE = 64            # indices per workgroup, at most (TPHU_PW_RT)
 POINTWISE_MIN_WORKGROUPS = 1024
 POINTWISE_SCRATCH_WORDS = 1 << 23  # 64 MiB of batch scratch at most: more indices than fit go through in batches
+# replicated(): the noise of replicate(x, r, g) is Philox at (item = row, draw = k >> 1, tick = r, tag), these two tags for g.normal /
+# g.uniform (1 .. 9 are taken: csrc/common.h, oracle/philox.py); its sums over rows run in PREDICT_SUM_LAYOUT, discrepancy's sum over
+# r in SUM_LAYOUT; tiles by predict_tiles.
+REPLICATE_TAGS = (10, 11)
 POINTWISE_KEYS = ("lppd", "mean", "p_waic", "elpd_waic", "elpd_loo", "ess_loo")      # the rows of tphu_pointwise's output
 
 
@@ -146,6 +150,59 @@ def _check_n_predict(source, n_predict, host) -> int:
     if isinstance(n_predict, bool) or not isinstance(n_predict, (int, np.integer)) or not 0 < int(n_predict) < 2 ** 31:
         raise ValueError(f"HipCallbacks: n_predict must be a positive int or the name of a data entry, got {n_predict!r}")
     return int(n_predict)
+
+
+def _has_replicate(source: str) -> bool:
+    """The source DEFINES replicate (`double replicate(`): the word alone, in a comment or a name, is not a definition."""
+    return re.search(r"\bdouble\s+replicate\s*\(", source) is not None
+
+
+def _has_discrepancy(source: str) -> bool:
+    """The source DEFINES discrepancy (`double discrepancy(`)."""
+    return re.search(r"\bdouble\s+discrepancy\s*\(", source) is not None
+
+
+def _check_n_replicate(source, n_replicate, observed, host):
+    """(n_replicate, name of the observed entry or None, the source has discrepancy()) of a checked HipCallbacks(n_replicate=, observed=)."""
+    has, disc = _has_replicate(source), _has_discrepancy(source)
+    if n_replicate is None:
+        if has:
+            raise ValueError("HipCallbacks: the source defines replicate(...): give n_replicate= (an int, or the name of a data entry)")
+        if observed is not None:
+            raise ValueError("HipCallbacks: observed= goes with a source that defines replicate(...) (and n_replicate=)")
+        if disc:
+            raise ValueError("HipCallbacks: the source defines discrepancy(...): it goes with a source that defines replicate(...) "
+                             "(and n_replicate=, observed=)")
+        return 0, None, False
+    if not has:
+        raise ValueError("HipCallbacks: n_replicate= goes with a source that defines __device__ double replicate(const double* x, int64_t r, "
+                         "const tphu_noise& g)")
+    if isinstance(n_replicate, str):
+        if n_replicate not in host:
+            raise ValueError(f"HipCallbacks: n_replicate={n_replicate!r} names no data entry")
+        n_rep = int(host[n_replicate].shape[0])
+    elif isinstance(n_replicate, bool) or not isinstance(n_replicate, (int, np.integer)) or not 0 < int(n_replicate) < 2 ** 31:
+        raise ValueError(f"HipCallbacks: n_replicate must be a positive int or the name of a data entry, got {n_replicate!r}")
+    else:
+        n_rep = int(n_replicate)
+    if observed is not None:
+        if not isinstance(observed, str) or observed not in host:
+            raise ValueError(f"HipCallbacks: observed={observed!r} names no data entry")
+        if host[observed].ndim != 1 or host[observed].shape[0] != n_rep:
+            raise ValueError(f"HipCallbacks: observed={observed!r} must be a 1-D data entry of length n_replicate = {n_rep}, got shape "
+                             f"{host[observed].shape}")
+    elif disc:
+        raise ValueError("HipCallbacks: the source defines discrepancy(...): give observed= (the name of the data entry it is compared on)")
+    return n_rep, observed, disc
+
+
+def replicate_scratch_words(n: int, n_replicate: int, n_q: int) -> int:
+    """8-byte words of scratch tphu_replicated gets for this call: W, the block sums of w, sum k, the p-value count, the PIT counters,
+    the chunk and block sums of u T, and for a batch of indices what predictive() keeps -- all n_replicate indices, or as many as
+    PREDICT_SCRATCH_WORDS hold."""
+    n_blocks = -(-n // (PREDICT_SUM_LAYOUT[0] * PREDICT_SUM_LAYOUT[1]))
+    per_r = n_blocks + 258 * n_q + 1
+    return 3 + 3 * n_blocks + 3 * n_replicate + 2 * -(-n // PREDICT_SUM_LAYOUT[0]) + per_r * min(n_replicate, max(1, PREDICT_SCRATCH_WORDS // per_r))
 
 
 def predict_tiles(n: int, n_predict: int, n_q: int):
@@ -259,21 +316,24 @@ def _struct_text(tables) -> str:
 
 
 def plugin_source(source: str, tables=None, term: bool = False, *, derived: bool = False, predict: bool = False,
-                  pointwise: bool = False) -> str:
+                  pointwise: bool = False, replicate: bool = False) -> str:
     """The translation unit for `source`.  tables None: callbacks of x alone (the template as it always was, byte for byte);
     ((name, rank), ...): the callbacks take `const tphu_data& D` and every kernel and entry point carries the table;
     term: the source gives log_likelihood_term and the library owns the sum; derived: the source gives derived(x, out) and the
     plugin gets k_user_derived / tphu_derived (compiled with -DN_DERIVED=k); predict: the source gives predict(x, r) and the plugin
     gets the k_user_predict_* kernels / tphu_predictive (compiled with -DTPHU_PREDICT); pointwise (term form only): the plugin gets
-    the k_user_pw_* kernels / tphu_pointwise (compiled with -DTPHU_POINTWISE)."""
+    the k_user_pw_* kernels / tphu_pointwise (compiled with -DTPHU_POINTWISE); replicate: the source gives replicate(x, r, g) and the
+    plugin gets tphu_noise, the k_user_rep_* kernels / tphu_replicated (compiled with -DTPHU_REPLICATE, and -DTPHU_DISCREPANCY where
+    the source also gives discrepancy())."""
     text = _TEMPLATE.read_text()
     if term and tables is None:
         tables = ()
     # lines of the data / term form / a source with derived() / with predict() / with pointwise=True only: dropped whole otherwise
     # (//@Q: what predict and pointwise share -- the layout constants, the row loads, the sum of the weights; //@R: the helpers a
-    # traced source calls, tempest_amd.trace)
-    keep = {"//@D": tables is not None, "//@T": term, "//@X": derived, "//@P": predict, "//@W": pointwise,
-            "//@Q": predict or pointwise, "//@R": re.search(r"\btphu_tr_(max|min)\s*\(", source) is not None}
+    # traced source calls, tempest_amd.trace; //@Y: a source with replicate(); //@S: what predict and replicate share -- the fold of
+    # the block sums, the select's key and its narrowing kernel)
+    keep = {"//@D": tables is not None, "//@T": term, "//@X": derived, "//@P": predict, "//@W": pointwise, "//@Y": replicate,
+            "//@S": predict or replicate, "//@Q": predict or pointwise or replicate, "//@R": re.search(r"\btphu_tr_(max|min)\s*\(", source) is not None}
     out = []
     for line in text.split("\n"):
         if line[:4] in keep and line[4:5] in ("", " "):
@@ -289,9 +349,9 @@ def plugin_source(source: str, tables=None, term: bool = False, *, derived: bool
         text = text.replace(mark, val if on else "")
     if on:
         text = text.replace("@DATA_STRUCT@", _struct_text(tables))
-    if term:
+    if term or replicate:
         text = text.replace("@TPHU_CHUNK@", str(SUM_LAYOUT[0])).replace("@TPHU_BLOCK@", str(SUM_LAYOUT[1]))
-    if predict or pointwise:
+    if predict or pointwise or replicate:
         text = text.replace("@TPHU_PCHUNK@", str(PREDICT_SUM_LAYOUT[0])).replace("@TPHU_PBLOCK@", str(PREDICT_SUM_LAYOUT[1]))
     return text.replace("@USER_SOURCE@", source)
 
@@ -312,19 +372,29 @@ def _toolchain_id() -> str:
     return _TOOLCHAIN
 
 
+def plugin_key(n_dim: int, *, n_derived: int = 0, predict: bool = False, pointwise: bool = False, replicate: bool = False,
+               discrepancy: bool = False) -> str:
+    """What build_plugin hashes beside the text and the headers: dimension, architecture, flags, toolchain, and a word per optional
+    part -- present only where the source has that part, so every other source keeps the key it had."""
+    return f"|{n_dim}|{_ARCH}|{' '.join(_FLAGS)}|{_toolchain_id()}" + (f"|derived={int(n_derived)}" if n_derived > 0 else "") \
+        + ("|predict" if predict else "") + ("|pointwise" if pointwise else "") + ("|replicate" if replicate else "") \
+        + ("|discrepancy" if replicate and discrepancy else "")
+
+
 def build_plugin(source: str, n_dim: int, verbose: bool = False, tables=None, term: bool = False, *, n_derived: int = 0,
-                 predict: bool = False, pointwise: bool = False) -> Path:
+                 predict: bool = False, pointwise: bool = False, replicate: bool = False, discrepancy: bool = False) -> Path:
     """Compile (or find in the cache) the plugin for `source`; returns the path of the shared library.  `tables` / `term` as in
     plugin_source: names, ranks and the element type of the data entries are in the generated text and so in the key; values and
     extents are not -- one compile serves every data set of that shape of table.  n_derived > 0: the source has derived(); only then
     do -DN_DERIVED and its part of the key exist, so every other source keeps the file name it had; the same holds for predict
-    (the source has predict()): -DTPHU_PREDICT and "|predict" in the key only then; and for pointwise (-DTPHU_POINTWISE, "|pointwise")."""
-    text = plugin_source(source, tables, term, derived=n_derived > 0, predict=predict, pointwise=pointwise)
+    (the source has predict()): -DTPHU_PREDICT and "|predict" in the key only then; for pointwise (-DTPHU_POINTWISE, "|pointwise"); and for
+    replicate (the source has replicate(): -DTPHU_REPLICATE, "|replicate"; with discrepancy() too: -DTPHU_DISCREPANCY, "|discrepancy")."""
+    text = plugin_source(source, tables, term, derived=n_derived > 0, predict=predict, pointwise=pointwise, replicate=replicate)
     defs = [f"-DN_DIM={int(n_dim)}"] + ([f"-DN_DERIVED={int(n_derived)}"] if n_derived > 0 else []) + (["-DTPHU_PREDICT"] if predict else []) \
-        + (["-DTPHU_POINTWISE"] if pointwise else [])
+        + (["-DTPHU_POINTWISE"] if pointwise else []) + (["-DTPHU_REPLICATE"] if replicate else []) \
+        + (["-DTPHU_DISCREPANCY"] if replicate and discrepancy else [])
     deps = (_CSRC / "common.h").read_bytes() + (_CSRC.parent.parent / "include" / "tempest_hip.h").read_bytes()
-    key = f"|{n_dim}|{_ARCH}|{' '.join(_FLAGS)}|{_toolchain_id()}" + (f"|derived={int(n_derived)}" if n_derived > 0 else "") \
-        + ("|predict" if predict else "") + ("|pointwise" if pointwise else "")
+    key = plugin_key(n_dim, n_derived=n_derived, predict=predict, pointwise=pointwise, replicate=replicate, discrepancy=discrepancy)
     tag = hashlib.sha256(text.encode() + deps + key.encode()).hexdigest()[:20]
     name = f"tphu_{n_dim}d_{tag}.so"
     for d in _cache_dirs():
@@ -359,11 +429,12 @@ class HipCallbacks:
     n_derived, derived_tile = 0, 0
     n_predict, predict_tile, predict_sum_layout = 0, 0, PREDICT_SUM_LAYOUT
     pointwise_enabled, pointwise_tile = False, 0
-    _device = _dev_tables = _dstruct = _bsum = _pscratch = _wscratch = None
+    n_replicate, observed, has_discrepancy = 0, None, False
+    _device = _dev_tables = _dstruct = _bsum = _pscratch = _wscratch = _yscratch = None
 
     def __init__(self, source: str, n_dim: int, fused: bool = True, verbose: bool = False, whole_step: bool = True,
                  persistent: bool = False, data=None, n_terms=None, n_derived=None, n_predict=None, *,
-                 pointwise=False):
+                 pointwise=False, n_replicate=None, observed=None):
         if not isinstance(n_dim, int) or n_dim <= 0:
             raise ValueError(f"n_dim must be a positive int, got {n_dim!r}")
         for fn in ("prior_transform", "log_likelihood"):
@@ -393,6 +464,8 @@ class HipCallbacks:
         # > 0 pins the indices per workgroup of predictive() (1 .. 64); (tile, slab) also the rows per workgroup of its select
         self.predict_tile = 0
         self._pscratch = None
+        self.n_replicate, self.observed, self.has_discrepancy = _check_n_replicate(source, n_replicate, observed, self._host)
+        self._yscratch = None
         self.n_terms = 0
         if has_term:
             if isinstance(n_terms, str):
@@ -424,7 +497,7 @@ class HipCallbacks:
         self.persistent = bool(persistent) if env is None else env != "0"
         self.run_groups = 0                    # > 0 limits the workgroups of that launch (tests: several tiles per workgroup)
         self.path = build_plugin(source, n_dim, verbose, self.tables, self.term, n_derived=self.n_derived, predict=bool(self.n_predict),
-                                 pointwise=self.pointwise_enabled)
+                                 pointwise=self.pointwise_enabled, replicate=bool(self.n_replicate), discrepancy=self.has_discrepancy)
         import torch  # noqa: F401  (its HIP runtime must be the one in the process, as for libtempest_hip)
         lib = C.CDLL(str(self.path))
         ptr, i64 = C.c_void_p, C.c_int64
@@ -451,6 +524,10 @@ class HipCallbacks:
             lib.tphu_pointwise.argtypes = [ptr, ptr, ptr, i64, i64, ptr, ptr, i64, C.c_int]
             fns.append(lib.tphu_pointwise)
             lib.tphu_pointwise_layout.argtypes, lib.tphu_pointwise_layout.restype = [C.c_int], C.c_int
+        if self.n_replicate:
+            lib.tphu_replicated.argtypes = [ptr, ptr, ptr, i64, i64, ptr, C.c_int, C.c_uint64, ptr, C.c_int, ptr, ptr, i64, C.c_int, i64]
+            fns.append(lib.tphu_replicated)
+            lib.tphu_replicate_layout.argtypes, lib.tphu_replicate_layout.restype = [C.c_int], C.c_int
         if self.tables is not None:            # a data-carrying plugin: every entry point takes the host copy of tphu_data last
             for f in fns:
                 f.argtypes = list(f.argtypes) + [ptr]
@@ -477,6 +554,9 @@ class HipCallbacks:
             raise TempestHipError(f"plugin {self.path}: predict() sum layout or tile limits do not match this package")
         if self.pointwise_enabled and tuple(lib.tphu_pointwise_layout(i) for i in range(3)) != PREDICT_SUM_LAYOUT + (POINTWISE_MAX_TILE,):
             raise TempestHipError(f"plugin {self.path}: pointwise sum layout or tile limit does not match this package")
+        if self.n_replicate and tuple(lib.tphu_replicate_layout(i) for i in range(8)) != PREDICT_SUM_LAYOUT + (PREDICT_MAX_TILE, PREDICT_TABLES) \
+                + SUM_LAYOUT + REPLICATE_TAGS:
+            raise TempestHipError(f"plugin {self.path}: replicate() sum layouts, tile limits or RNG tags do not match this package")
         self.lib = lib
 
     # ---------------------------------------------------------------------------------- data tables
@@ -715,6 +795,51 @@ class HipCallbacks:
                     "tphu_predictive")
         res = out.cpu().numpy()
         return {"mean": res[0].copy(), "var": res[1].copy(), "quantiles": res[2:].copy(), "n_rows": n, "ess": s1 * s1 / s2}
+
+    def replicated(self, x, w, quantiles=(0.025, 0.5, 0.975), seed=0):
+        """Posterior predictive check with replicated data y_rep[i, r] = replicate(x_i, r, g), r = 0 .. n_replicate - 1, over the (n,
+        n_dim) points x with weights w (as predictive(): >= 0, finite, positive sum; torch-ROCm tensors or NumPy arrays; n < 2^32): a
+        dict of NumPy arrays "mean", "var" (n_replicate,), "quantiles" (len(quantiles), n_replicate) -- the weighted inverted CDF of
+        y_rep[:, r] --, and "n_rows", "ess", "seed"; with observed=: "pit" (n_replicate,), the weighted share of y_rep[:, r] below the
+        observed y_r plus half the share equal to it (NaN where a replicate with weight, or y_r, is NaN); with discrepancy() in the
+        source: "p_value" = the weighted share of rows with T_rep_i >= T_obs_i, "t_obs_mean", "t_rep_mean" (floats), T_. the sums of
+        discrepancy over r at the observed and the replicated values.  The draws of g belong to (seed, the row's INDEX i in x, r): the
+        same call gives the same bits, and permuting the rows (with their weights) gives another -- equally valid -- set of draws.
+        Nothing of size n x n_replicate is formed.  The scratch is one buffer kept on this object."""
+        import torch
+        if not self.n_replicate:
+            raise TempestHipError("HipCallbacks.replicated: the source defines no replicate(...) (give it and n_replicate=)")
+        qs = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
+        if qs.ndim != 1 or len(qs) > MAX_QUANTILES or not np.all((qs >= 0.0) & (qs <= 1.0)):
+            raise ValueError(f"replicated: quantiles must be at most {MAX_QUANTILES} numbers in [0, 1], got {quantiles!r}")
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
+            raise ValueError(f"replicated: seed must be an int in [0, 2^64), got {seed!r}")
+        x, w, n, s1, s2 = self._rows_and_weights(x, w, "replicated")
+        if n >= 2 ** 32:
+            raise ValueError(f"replicated: at most 2^32 - 1 rows (the row index is a 32-bit counter word of the noise), got {n}")
+        R, nq = self.n_replicate, len(qs)
+        pin = self.predict_tile
+        tile, slab = predict_tiles(n, R, nq)
+        if pin:
+            tile, slab = (int(pin[0]), int(pin[1])) if isinstance(pin, (tuple, list)) else (int(pin), slab)
+        words = replicate_scratch_words(n, R, nq)
+        if self._yscratch is None or self._yscratch.numel() < words or self._yscratch.device != x.device:
+            self._yscratch = torch.empty(words, dtype=torch.int64, device=x.device)      # kept: no allocation per call
+        out = torch.empty((3 + nq) * R + 3, dtype=torch.float64, device=x.device)
+        data = self._data()
+        obs = self._dev_tables[self.observed].data_ptr() if self.observed is not None else None
+        self._check(self.lib.tphu_replicated(self._stream(x), x.data_ptr(), w.data_ptr(), n, R, qs.ctypes.data, nq, int(seed), obs,
+                                             1 if self.has_discrepancy else 0, out.data_ptr(), self._yscratch.data_ptr(),
+                                             self._yscratch.numel(), tile, slab, *data), "tphu_replicated")
+        flat = out.cpu().numpy()
+        res = flat[:(3 + nq) * R].reshape(3 + nq, R)
+        ret = {"mean": res[0].copy(), "var": res[1].copy(), "quantiles": res[2:2 + nq].copy(), "n_rows": n, "ess": s1 * s1 / s2,
+               "seed": int(seed)}
+        if self.observed is not None:
+            ret["pit"] = res[2 + nq].copy()
+        if self.has_discrepancy:
+            ret.update(p_value=float(flat[-3]), t_obs_mean=float(flat[-2]), t_rep_mean=float(flat[-1]))
+        return ret
 
     def pointwise(self, x, w):
         """Pointwise log predictive densities of a term-form source built with pointwise=True, over the (n, n_dim) points x with

@@ -144,6 +144,17 @@ class Sampler:
         return self._core.compute_predictive(quantiles=quantiles, trim_importance_weights=trim_importance_weights,
                                              ess_trim=ess_trim, bins_trim=bins_trim)
 
+    def replicated(self, quantiles=(0.025, 0.5, 0.975), seed: Optional[int] = None, trim_importance_weights: bool = True,
+                   ess_trim: float = 0.99, bins_trim: int = 1000) -> dict:
+        """Posterior predictive check of a HipCallbacks source's replicate(x, r, g), r = 0 .. n_replicate - 1, over the weighted rows
+        posterior() returns, in its row order: {"mean", "var": (n_replicate,), "quantiles": (len(quantiles), n_replicate), "n_rows",
+        "ess", "seed"}, with observed= "pit" (n_replicate,), with discrepancy() "p_value", "t_obs_mean", "t_rep_mean", NumPy
+        (HipCallbacks.replicated; the same numbers as cb.replicated(x, w, seed=seed) on posterior()'s x and w).  seed None: the run's
+        seed.  The rows stay on the device; nothing of size rows x n_replicate is formed.  Not available on a sharded run
+        (NotImplementedError)."""
+        return self._core.compute_replicated(quantiles=quantiles, seed=seed, trim_importance_weights=trim_importance_weights,
+                                             ess_trim=ess_trim, bins_trim=bins_trim)
+
     def pointwise(self, trim_importance_weights: bool = True, ess_trim: float = 0.99, bins_trim: int = 1000) -> dict:
         """Pointwise log predictive densities of a HipCallbacks term-form source built with pointwise=True, over the weighted rows
         posterior() returns: {"lppd", "mean", "p_waic", "elpd_waic", "elpd_loo", "ess_loo": (n_terms,), "n_rows", "ess", "totals"},

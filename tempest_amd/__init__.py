@@ -4,7 +4,7 @@ __version__ = "0.1.0"
 
 from .sampler import Sampler
 
-__all__ = ["Sampler", "HipCallbacks", "trace_callbacks"]
+__all__ = ["Sampler", "HipCallbacks", "trace_callbacks", "Noise"]
 
 
 def __getattr__(name):          # lazy: importing the package must not need hipcc or a GPU
@@ -14,4 +14,7 @@ def __getattr__(name):          # lazy: importing the package must not need hipc
     if name == "trace_callbacks":
         from .trace import trace_callbacks
         return trace_callbacks
+    if name == "Noise":         # the host twin of a plugin's tphu_noise: the g of trace_callbacks(replicate=) in eager use
+        from .trace import Noise
+        return Noise
     raise AttributeError(name)

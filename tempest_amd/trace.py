@@ -20,6 +20,11 @@ Likelihoods over observed data (`data=`, `n_terms=`, `predict=`): the callbacks 
 function (x, D) -> (n, n_terms) returns one column per observation and is emitted as `log_likelihood_term(x, r, D)`, the column at
 the term index r -- the library owns the sum.  Under the tracer an entry has no particle axis: one as long as the term axis is a
 value per term (`D.t[r]`), so is a column of a 2-D entry and `xs @ D["X"].T`; constant integer indices read one element.
+
+Replicated data (`replicate=`, `n_replicate=`, `observed=`, `discrepancy=`): replicate (x, D, g) -> (n, n_replicate) draws its noise
+from g.normal(k) / g.uniform(k), leaf nodes emitted as the calls of the plugin's `tphu_noise`; discrepancy (x, y, D) -> (n,
+n_replicate) gets the term-valued y.  `Noise` is the host twin of the device's counter-based stream, for the eager side of the probe
+and for `replay(..., noise=, y=)`.
 """
 import linecache
 import math
@@ -89,14 +94,17 @@ _UNARY = {"abs": "fabs", "sqrt": "sqrt", "rsqrt": "rsqrt", "exp": "exp", "expm1"
           "sin": "sin", "cos": "cos", "tan": "tan", "tanh": "tanh", "atan": "atan", "erf": "erf", "erfc": "erfc", "lgamma": "lgamma"}
 _COMPARE = {"gt": ">", "lt": "<", "ge": ">=", "le": "<=", "eq": "==", "ne": "!="}
 _BOOL_OPS = set(_COMPARE) | {"and", "or", "not"}
-_LEAF = ("in", "const", "dterm", "delem")         # nodes without operand nodes: what follows the op are plain ints
+_NOISE = {"noise_normal": "normal", "noise_uniform": "uniform"}
+_LEAF = ("in", "const", "dterm", "delem", "yarg") + tuple(_NOISE)    # nodes without operand nodes: what follows the op are plain ints
 _UNINIT = -1
 
 
 class Graph:
     """nodes[i] = (op, operands): "in" (column,), "const" (the double's 64 bits,), "dterm" (table, column) -- the data entry at
     position `table` of the spec read at the term index r: D.name[r], or D.name[r * D.name_cols + column] (column -1: a 1-D entry)
-    --, "delem" (table, i, j) -- the element D.name[i] (j = -1) or D.name[i * D.name_cols + j] --, else indices of earlier nodes.
+    --, "delem" (table, i, j) -- the element D.name[i] (j = -1) or D.name[i * D.name_cols + j] --, "noise_normal" / "noise_uniform" (k,)
+    -- the draw g.normal(k) / g.uniform(k) of replicate, a value per (particle, r) --, "yarg" () -- the y of discrepancy, a value per
+    (particle, r) --, else indices of earlier nodes.
     outputs: the node of every output value in row-major order of out_shape (the trailing shape: () for one value per particle).
     tables: ((name, rank), ...) of the data entries; n_term: the extent of the term axis (None: a callback without one), term_name
     its name ("n_terms" / "n_predict"); reads: {entry: {how it is read}}."""
@@ -177,6 +185,10 @@ def emit(graph, signature, inp, store, r="r"):
             rhs = _literal(graph.value(i))
         elif op in ("dterm", "delem"):
             rhs = _data_read(graph, op, args, r)
+        elif op in _NOISE:
+            rhs = f"g.{_NOISE[op]}({args[0]})"
+        elif op == "yarg":
+            rhs = "y"
         elif op in _BINARY:
             rhs = f"{t[0]} {_BINARY[op]} {t[1]}"
         elif op in _CALL2:
@@ -209,10 +221,16 @@ def _torch_unary(name):
     return lambda a: fn(torch.from_numpy(np.ascontiguousarray(a))).numpy()
 
 
-def replay(graph, array, data=None):
+def _host_array(v):
+    return np.asarray(v.detach().cpu().numpy() if _is_tensor(v) else v, dtype=np.float64)
+
+
+def replay(graph, array, data=None, noise=None, y=None):
     """The graph evaluated in NumPy float64, node by node in emission order, on the (n, n_in) rows of `array`: what the emitted
-    device function computes -- (n,) + graph.out_shape; (n, T) for a term or predict graph, whose nodes are evaluated for every
-    (row, term index) -- the device function is called once per pair.  data: {name: array} for graphs that read data entries.
+    device function computes -- (n,) + graph.out_shape; (n, T) for a term, predict, replicate or discrepancy graph, whose nodes are
+    evaluated for every (row, term index) -- the device function is called once per pair.  data: {name: array} for graphs that read
+    data entries; noise: a `Noise` over the n rows (anything with .normal(k) / .uniform(k) -> (n, T)) for a replicate graph that
+    draws; y: (T,) -- one row for all -- or (n, T), the y of a discrepancy graph.
     exp, log and the other transcendentals, erf, erfc and lgamma come from torch on the CPU."""
     a = np.ascontiguousarray(array, dtype=np.float64)
     if a.ndim != 2 or a.shape[1] != graph.n_in:
@@ -249,6 +267,19 @@ def replay(graph, array, data=None):
                 if not per_term or t.shape[0] != graph.n_term:
                     raise ValueError(f"replay: data[{graph.tables[args[0]][0]!r}] has {t.shape[0]} rows, traced with {graph.n_term}")
                 val[i] = (t if args[1] < 0 else np.ascontiguousarray(t[:, args[1]]))[None, :]
+            elif op in _NOISE:
+                if noise is None:
+                    raise ValueError("replay: this graph draws noise: give noise=Noise(seed, items, n_replicate)")
+                val[i] = _host_array(getattr(noise, _NOISE[op])(args[0]))
+                if val[i].shape != (n, graph.n_term):
+                    raise ValueError(f"replay: noise.{_NOISE[op]}({args[0]}) has shape {val[i].shape}, expected {(n, graph.n_term)}")
+            elif op == "yarg":
+                if y is None:
+                    raise ValueError("replay: this graph reads y: give y= (n_replicate,) or (n, n_replicate)")
+                val[i] = _host_array(y)
+                if val[i].shape not in ((graph.n_term,), (n, graph.n_term)):
+                    raise ValueError(f"replay: y has shape {val[i].shape}, expected {(graph.n_term,)} or {(n, graph.n_term)}")
+                val[i] = val[i][None, :] if val[i].ndim == 1 else val[i]
             elif op in bi:
                 val[i] = bi[op](val[args[0]], val[args[1]])
             elif op in un:
@@ -1134,31 +1165,135 @@ def _wants_data(fn):
     return sum(p.kind in (p.POSITIONAL_ONLY, p.POSITIONAL_OR_KEYWORD) for p in ps) >= 2
 
 
+# ------------------------------------------------------------------------------------------------------ noise
+MAX_DRAW = 2 ** 31              # k of g.normal(k) / g.uniform(k): the device takes it as an int
+
+
+def _draw_index(k):
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 0 <= int(k) < MAX_DRAW:
+        return None
+    return int(k)
+
+
+class _NoiseArg:
+    """The g of replicate(x, D, g) under the tracer: g.normal(k) / g.uniform(k) are leaf nodes, one per distinct (kind, k), each a
+    value per (particle, r) -- shape (n, n_replicate)."""
+
+    def __init__(self, g):
+        self._g = g
+
+    def _draw(self, kind, k):
+        i = _draw_index(k)
+        if i is None:
+            _refuse(f"g.{kind}({k!r})", "the index of a draw is a constant of the emitted code: a Python int with 0 <= k < 2^31 (the "
+                    "draw belongs to (seed, row, r, k); a traced value, a float or a negative number names none)",
+                    f"g.{kind}(0), g.{kind}(1), ...: one constant int per independent draw")
+        return TV(self._g, self._g.add("noise_" + kind, i), term=True)
+
+    def normal(self, k):
+        return self._draw("normal", k)
+
+    def uniform(self, k):
+        return self._draw("uniform", k)
+
+    def __getattr__(self, name):
+        if name.startswith("_"):
+            raise AttributeError(name)
+        _refuse(f"g.{name}", "the noise object has g.normal(k) and g.uniform(k) and nothing else", "compose the law from them: a "
+                "Bernoulli is torch.where(g.uniform(k) < p, 1.0, 0.0)")
+
+
+class Noise:
+    """The host twin of the device's `tphu_noise`: Noise(seed, items, n_replicate).normal(k) / .uniform(k) are (len(items),
+    n_replicate) float64 tensors (on `device`; default: the CPU) whose element [i, r] is the draw g.normal(k) / g.uniform(k) the
+    device hands replicate(x, r, g) for the row of index items[i] in the x that cb.replicated(x, w, seed=seed) was given.  Philox4x32-10
+    with key = seed, counter (item = the row's index, draw = k >> 1, tick = r, tag = 10 for normals, 11 for uniforms), lane k & 1 of
+    the pair.
+
+    The uniforms are 53-bit integers scaled by 2^-53: they EQUAL the device's bits.  The normals are Box-Muller on the same two
+    uniforms, r = sqrt(-2 log u1), angle 2 pi u2, with NumPy's log / cos / sin where the device has its own lean versions: they agree
+    with the device's to rounding, not to the bit.  A function that thresholds a normal (g.normal(k) > c) can therefore differ
+    from the device at a tie; one that thresholds a uniform cannot.  The same k asked twice is the same tensor."""
+
+    def __init__(self, seed, items, n_replicate, device=None):
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
+            raise ValueError(f"Noise: seed must be an int in [0, 2^64), got {seed!r}")
+        if isinstance(n_replicate, bool) or not isinstance(n_replicate, (int, np.integer)) or not 0 < int(n_replicate) < 2 ** 31:
+            raise ValueError(f"Noise: n_replicate must be an int in (0, 2^31), got {n_replicate!r}")
+        items = np.asarray(items)
+        if items.ndim != 1 or items.dtype.kind not in "iu" or (items.size and (int(items.min()) < 0 or int(items.max()) >= 2 ** 32)):
+            raise ValueError("Noise: items must be a 1-D array of row indices in [0, 2^32)")
+        self.seed, self.n_replicate, self.device = int(seed), int(n_replicate), device
+        self.items = items.astype(np.uint64)
+        self._pairs, self._out = {}, {}
+
+    def _get(self, kind, k):
+        import torch
+        from ._philox_host import normal_pair, uniform_pair
+        from .hipcallbacks import REPLICATE_TAGS
+        i = _draw_index(k)
+        if i is None:
+            raise ValueError(f"Noise.{kind}: k must be an int with 0 <= k < 2^31, got {k!r}")
+        if (kind, i) not in self._out:
+            if (kind, i >> 1) not in self._pairs:
+                pair, tag = (normal_pair, REPLICATE_TAGS[0]) if kind == "normal" else (uniform_pair, REPLICATE_TAGS[1])
+                self._pairs[(kind, i >> 1)] = pair(self.seed, self.items[:, None], i >> 1, np.arange(self.n_replicate, dtype=np.uint64)[None, :], tag)
+            t = torch.from_numpy(np.ascontiguousarray(self._pairs[(kind, i >> 1)][i & 1]))
+            self._out[(kind, i)] = t if self.device is None else t.to(self.device)
+        return self._out[(kind, i)]
+
+    def normal(self, k):
+        return self._get("normal", k)
+
+    def uniform(self, k):
+        return self._get("uniform", k)
+
+
 # ------------------------------------------------------------------------------------------------------ tracing
-def trace_function(fn, n_in, out_width=None, name=None, data=None, term=None, pass_data=None):
+def _defined_at(fn):
+    code = getattr(fn, "__code__", None)
+    if code is None:
+        return "<unknown>"
+    return f"{code.co_filename}:{code.co_firstlineno}: {linecache.getline(code.co_filename, code.co_firstlineno).strip()}"
+
+
+def trace_function(fn, n_in, out_width=None, name=None, data=None, term=None, pass_data=None, noise=False, yarg=False):
     """Run `fn` once on a symbolic (n, n_in) float64 input; returns its Graph.  out_width: an int -> (n, out_width) expected, () ->
     (n,) expected, None -> (n, k) or (n,) as it comes.  data: (((name, rank), ...), {name: (shape, is float64)}) -- the entries fn may
     read through its second argument D (pass_data: hand D over; default: whenever data is given); term: (extent, its name) -- fn
-    returns one column per term, (n, extent), and the graph computes the column at the term index r."""
+    returns one column per term, (n, extent), and the graph computes the column at the term index r.  noise: fn is a replicate
+    (x, D, g) -> (n, extent) and gets the noise object g behind D; yarg: fn is a discrepancy (x, y, D) -> (n, extent) and gets the
+    term-valued y before D.  Either returns doubles: a bool result is refused."""
     if not callable(fn):
         raise TypeError(f"trace_callbacks: expected a callable, got {type(fn).__name__}")
     name = name or getattr(fn, "__name__", "callback")
+    if (noise or yarg) and (data is None or term is None):
+        raise ValueError("trace_function: noise= / yarg= go with data= and term= (replicate and discrepancy read D and return (n, n_replicate))")
     g = Graph(n_in, name, *((data[0],) if data is not None else (None,)), *(term or ()))
     x = TV(g, [g.add("in", j) for j in range(n_in)], is_input=True)
     if data is not None and (pass_data is None or pass_data):
-        y = _call(fn, x, _Data((nm, _Entry(g, pos, nm, *data[1][nm])) for pos, (nm, _) in enumerate(data[0])))
+        D = _Data((nm, _Entry(g, pos, nm, *data[1][nm])) for pos, (nm, _) in enumerate(data[0]))
+        if noise:
+            y = _call(fn, x, D, _NoiseArg(g))
+        elif yarg:
+            y = _call(fn, x, TV(g, g.add("yarg"), term=True), D)
+        else:
+            y = _call(fn, x, D)
     else:
         y = _call(fn, x)
+    if (noise or yarg) and isinstance(y, TV) and y._bool():
+        _refuse(f"a bool result of {g.name}", "a replicated observation and a discrepancy are doubles on the device; a comparison is "
+                "a condition, not a value", "torch.where(condition, 1.0, 0.0)", at=_defined_at(fn))
     if not isinstance(y, TV) or not y.batch:
         raise TraceError(f"trace_callbacks: {g.name} returned {'a data value' if isinstance(y, TV) else type(y).__name__}, not a value "
                          "computed from its input with the supported torch operations")
     y = y._as_double()
     if term is not None:
         if not y.term or y.ids.ndim:
-            raise TraceError(f"trace_callbacks: {g.name} returned {tuple(y.shape)}, expected (n, {g.term_extent!r}): one column per "
+            raise TraceError((f"trace_callbacks: {g.name} returned {tuple(y.shape)}, expected (n, {g.term_extent!r}): one column per "
                              f"term, the result has no term axis of its own" if not y.term else
                              f"trace_callbacks: {g.name} returned {tuple(y.shape)}, expected (n, {g.term_extent!r}): reduce the other "
-                             "axes (dim=1) first")
+                             "axes (dim=1) first") + (f"\n  at {_defined_at(fn)}" if noise or yarg else ""))
     elif y.ids.ndim > 1 or (out_width is not None and y.ids.shape != ((out_width,) if out_width != () else ())):
         want = "(n, k) or (n,)" if out_width is None else f"(n, {out_width})" if out_width != () else "(n,)"
         raise TraceError(f"trace_callbacks: {g.name} returned (n,{','.join(map(str, y.ids.shape))}), expected {want}"
@@ -1170,7 +1305,9 @@ def trace_function(fn, n_in, out_width=None, name=None, data=None, term=None, pa
 
 def emit_source(graphs, tables=None):
     """The HipCallbacks source for {"prior_transform": Graph, "log_likelihood" | "log_likelihood_term": Graph[, "predict": Graph]
-    [, "derived": Graph]}.  tables: the data entries -- every signature then carries `const tphu_data& D`, as hand-written ones do."""
+    [, "derived": Graph][, "replicate": Graph[, "discrepancy": Graph]]}.  tables: the data entries -- every signature then carries
+    `const tphu_data& D`, as hand-written ones do.  A draw of replicate is `g.normal(k)` / `g.uniform(k)`, called once per distinct
+    (kind, k); discrepancy uses its `y` directly."""
     D = "" if tables is None else ", const tphu_data& D"
     parts = ["// emitted by tempest_amd.trace_callbacks (DESIGN.md section 11): values live in registers, one statement per graph node"]
     parts.append(emit(graphs["prior_transform"], f"__device__ void prior_transform(const double* u, double* x{D})", "u",
@@ -1185,6 +1322,12 @@ def emit_source(graphs, tables=None):
     if "derived" in graphs:
         parts.append(emit(graphs["derived"], f"__device__ void derived(const double* x, double* out{D})", "x",
                           lambda k, t: f"out[{k}] = {t};"))
+    if "replicate" in graphs:
+        parts.append(emit(graphs["replicate"], f"__device__ double replicate(const double* x, int64_t r, const tphu_noise& g{D})", "x",
+                          lambda k, t: f"return {t};"))
+    if "discrepancy" in graphs:
+        parts.append(emit(graphs["discrepancy"], f"__device__ double discrepancy(const double* x, int64_t r, double y{D})", "x",
+                          lambda k, t: f"return {t};"))
     return "\n".join(parts) + "\n"
 
 
@@ -1241,18 +1384,81 @@ def layered_sum(terms, chunk, block):
     return _seq_sum_last(t)
 
 
-def probe(cb, prior_transform, log_likelihood, derived=None, predict=None):
+def _probe_replicate(cb, graphs, data, x, on_device, report, replicate, discrepancy, D_on, chunks):
+    """The (name, eager, traced) pairs of replicate and discrepancy (see `probe`)."""
+    import torch
+    from .hipcallbacks import SUM_LAYOUT
+    R = cb.n_replicate
+    disc = discrepancy is not None and "discrepancy" in graphs
+    obs = data[cb.observed] if disc else None
+
+    def eager_on(dev, xs, items):
+        """(eager y_rep (n, R)[, eager T (n, 2)]) on `dev`."""
+        D, g, xt = D_on(dev), Noise(PROBE_SEED, items, R, device=dev), torch.from_numpy(np.ascontiguousarray(xs)).to(dev)
+        y = torch.as_tensor(replicate(xt, D, g))
+        out = [y.detach().cpu().numpy().astype(np.float64)]
+        if disc:
+            yo = D[cb.observed][None, :].expand(len(xs), R)
+            ts = [torch.as_tensor(discrepancy(xt, yy, D)).detach().cpu().numpy() for yy in (yo, y.to(torch.float64))]
+            out.append(np.stack([layered_sum(t, *SUM_LAYOUT) if t.shape == (len(xs), R) else np.full(len(xs), np.nan) for t in ts], axis=1))
+        return out
+
+    def eager(xs, items):
+        if on_device:
+            try:
+                report["eager_on"]["replicate"] = "device"
+                return eager_on(cb.device or "cuda", xs, items)
+            except RuntimeError as e:
+                if "Expected all tensors to be on the same device" not in str(e):
+                    raise
+        report["eager_on"]["replicate"] = "cpu"
+        return eager_on("cpu", xs, items)
+
+    ey, et, ty, tt = [], [], [], []
+    if on_device:                                    # at most 8 rows, each alone with weight 1: item 0, mean = replicate exactly
+        for i in range(min(8, len(x))):
+            got = cb.replicated(x[i:i + 1], np.ones(1), quantiles=(0.5,), seed=PROBE_SEED)
+            e = eager(x[i:i + 1], np.zeros(1, dtype=np.int64))
+            ey.append(e[0])
+            ty.append(np.asarray(got["mean"], dtype=np.float64)[None, :])
+            if disc:
+                et.append(e[1])
+                tt.append(np.array([[got["t_obs_mean"], got["t_rep_mean"]]], dtype=np.float64))
+    else:
+        for c in chunks(R):
+            items = np.arange(c.start, c.stop, dtype=np.int64)
+            e = eager(x[c], items)
+            y = replay(graphs["replicate"], x[c], data, noise=Noise(PROBE_SEED, items, R))
+            ey.append(e[0])
+            ty.append(y)
+            if disc:
+                et.append(e[1])
+                tt.append(np.stack([layered_sum(replay(graphs["discrepancy"], x[c], data, y=yy), *SUM_LAYOUT) for yy in (obs, y)], axis=1))
+    ok = all(a.shape == t.shape for a, t in zip(ey, ty))                                         # a wrong shape fails the comparison
+    pairs = [("replicate", np.concatenate(ey) if ok else np.full(1, np.nan), np.concatenate(ty))]
+    if disc:
+        pairs.append(("discrepancy", np.concatenate(et), np.concatenate(tt)))
+    return pairs
+
+
+def probe(cb, prior_transform, log_likelihood, derived=None, predict=None, replicate=None, discrepancy=None):
     """Compare the eager callables with the compiled plugin `cb` (with a device) or with the replay of its graphs (without) on the
     probe batch; returns the report, raises TraceError (with .source) where they disagree.  With data the eager functions get the
     float64 tensors the device tables hold; a term function's eager columns are summed by `layered_sum` and held against
     cb.log_likelihood (the replayed terms summed alike, without a device), in chunks of rows so that nothing larger than 2^22
-    doubles is formed; predict is checked through cb.predictive with one row of weight 1, which returns predict(x, .) exactly."""
+    doubles is formed; predict is checked through cb.predictive with one row of weight 1, which returns predict(x, .) exactly.
+    replicate and discrepancy are checked through cb.replicated(x_i, [1.0], seed=PROBE_SEED) in the same way, at most 8 rows: "mean"
+    is replicate(x_i, r, g) at item 0 exactly, "t_obs_mean" / "t_rep_mean" the layered sums of discrepancy at the observed and at
+    the replicated values; the eager functions get Noise(PROBE_SEED, [0], n_replicate).  Without a device the replay runs on
+    Noise(PROBE_SEED, the rows' indices, n_replicate), and so does the eager side.  The normals of Noise agree with the device's to
+    rounding only, which the tolerance absorbs; a replicate that thresholds a NORMAL could flip an element at a tie and fail the
+    probe on a correct trace (thresholding a uniform cannot: those bits are equal) -- the rule is not widened for it."""
     import torch
     from .hipcallbacks import SUM_LAYOUT
     graphs, d = cb.trace_graphs, cb.n_dim
     data = dict(cb._host) if cb.tables is not None else None
     term = "log_likelihood_term" in graphs
-    widest = max(cb.n_terms if term else 1, cb.n_predict if "predict" in graphs else 1)
+    widest = max(cb.n_terms if term else 1, cb.n_predict if "predict" in graphs else 1, cb.n_replicate if "replicate" in graphs else 1)
     rows = PROBE_ROWS if widest == 1 and not term else max(1, min(PROBE_ROWS, 2 ** 22 // widest))
     u = probe_batch(d, rows)
     on_device = torch.cuda.is_available()
@@ -1312,6 +1518,8 @@ def probe(cb, prior_transform, log_likelihood, derived=None, predict=None):
                 t = np.concatenate([replay(graphs["predict"], x[c], data) for c in chunks(cb.n_predict)])
             e = np.concatenate([eager("predict", predict, xs[c], True) for c in chunks(cb.n_predict) if len(xs[c])])
             pairs.append(("predict", e, t))
+        if replicate is not None and "replicate" in graphs:
+            pairs += _probe_replicate(cb, graphs, data, x, on_device, report, replicate, discrepancy, D_on, chunks)
         if derived is not None:
             e = eager("derived", derived, x, has and _wants_data(derived))
             pairs.append(("derived", e, traced("derived", x).reshape(e.shape) if e.size == x.shape[0] * cb.n_derived else None))
@@ -1356,7 +1564,8 @@ def _is_f64(a):
 
 
 def trace_callbacks(prior_transform, log_likelihood, n_dim, derived=None, check=True, *, data=None, n_terms=None, predict=None,
-                    n_predict=None, pointwise=False, **hipcallbacks_kwargs):
+                    n_predict=None, pointwise=False, replicate=None, n_replicate=None, observed=None, discrepancy=None,
+                    **hipcallbacks_kwargs):
     """The user's vectorised torch callbacks -- (n, d) float64 -> (n, d) and (n, d) -> (n,), unchanged -- as a HipCallbacks object:
     traced, emitted as HIP device functions, compiled by the usual HipCallbacks constructor.  derived: (n, d) -> (n, k) or (n,),
     becomes the source's derived(); check: run the probe (see `probe`).  cb.source holds the emitted text, cb.trace_report the op
@@ -1369,7 +1578,16 @@ def trace_callbacks(prior_transform, log_likelihood, n_dim, derived=None, check=
     the sum; without it, log_likelihood(x, D) -> (n,) may read elements D[name][j] only.  predict= (x, D) -> (n, n_predict) with
     n_predict= becomes the source's predict() (predict= without data= is refused: every column would have to be spelled out); pointwise=
     as in HipCallbacks.  A 1-D entry as long as the term axis is a value per term, used whole; a 2-D entry (T, k) gives columns
-    D[name][:, j] and xs @ D[name].T; constant integer indices read an element of any entry."""
+    D[name][:, j] and xs @ D[name].T; constant integer indices read an element of any entry.
+
+    replicate= (x, D, g) -> (n, n_replicate) with n_replicate= (as n_predict=) becomes the source's replicate(): one replicated
+    observation per column, its noise from g.normal(k) / g.uniform(k) -- k a constant Python int in [0, 2^31), each call a value per
+    (row, column), the draw tphu_noise::normal(k) / uniform(k) of (seed, row, r) on the device, the same k the same value.
+    observed= names the 1-D entry the replicates are compared with (PIT), as in HipCallbacks; discrepancy= (x, y, D) -> (n,
+    n_replicate), y (n, n_replicate) the observed row broadcast or the replicated matrix, becomes the source's discrepancy(): the
+    terms of the statistic, summed by the library in the term order -- no .sum().  replicate= needs data= and n_replicate=,
+    discrepancy= needs replicate= and observed=, observed= needs replicate=.  Neither may reduce or index along the replicate axis
+    or return a bool (torch.where(c, 1.0, 0.0)).  `Noise` is g on the host; cb.trace_report["draws"] lists the k that are drawn."""
     from .hipcallbacks import HipCallbacks, _table_spec
     if not isinstance(n_dim, (int, np.integer)) or isinstance(n_dim, bool) or n_dim <= 0:
         raise ValueError(f"n_dim must be a positive int, got {n_dim!r}")
@@ -1389,6 +1607,19 @@ def trace_callbacks(prior_transform, log_likelihood, n_dim, derived=None, check=
         raise ValueError("trace_callbacks: predict= needs n_predict= (an int, or the name of a data entry)")
     if pointwise and n_terms is None:
         raise ValueError("trace_callbacks: pointwise=True goes with n_terms= (a term function)")
+    if replicate is None and n_replicate is not None:
+        raise ValueError("trace_callbacks: n_replicate= goes with replicate= (a function (x, D, g) -> (n, n_replicate))")
+    if replicate is None and discrepancy is not None:
+        raise ValueError("trace_callbacks: discrepancy= goes with replicate= (and n_replicate=, observed=)")
+    if replicate is None and observed is not None:
+        raise ValueError("trace_callbacks: observed= goes with replicate= (and n_replicate=)")
+    if replicate is not None and data is None:
+        raise ValueError("trace_callbacks: replicate= without data= is not traced (every column would be an expression of its own): "
+                         "give what depends on the index as a data entry and n_replicate= its name")
+    if replicate is not None and n_replicate is None:
+        raise ValueError("trace_callbacks: replicate= needs n_replicate= (an int, or the name of a data entry)")
+    if discrepancy is not None and observed is None:
+        raise ValueError("trace_callbacks: discrepancy= needs observed= (the name of the data entry it is compared on)")
     wants = {"prior_transform": data is not None and _wants_data(prior_transform), "derived": data is not None and _wants_data(derived)}
     graphs = {"prior_transform": trace_function(prior_transform, n_dim, n_dim, "prior_transform", spec, pass_data=wants["prior_transform"])}
     if n_terms is not None:
@@ -1400,9 +1631,16 @@ def trace_callbacks(prior_transform, log_likelihood, n_dim, derived=None, check=
         graphs["predict"] = trace_function(predict, n_dim, None, "predict", spec, (_extent(n_predict, "n_predict", host), "n_predict"))
     if derived is not None:
         graphs["derived"] = trace_function(derived, n_dim, None, "derived", spec, pass_data=wants["derived"])
+    if replicate is not None:
+        extent = (_extent(n_replicate, "n_replicate", host), "n_replicate")
+        graphs["replicate"] = trace_function(replicate, n_dim, None, "replicate", spec, extent, noise=True)
+        if discrepancy is not None:
+            graphs["discrepancy"] = trace_function(discrepancy, n_dim, None, "discrepancy", spec, extent, yarg=True)
     source = emit_source(graphs, tables)
     n_derived = max(1, len(graphs["derived"].outputs)) if derived is not None else None
     data_kwargs = {} if data is None else {"data": host, "n_terms": n_terms, "n_predict": n_predict, "pointwise": bool(pointwise)}
+    if replicate is not None:
+        data_kwargs.update(n_replicate=n_replicate, observed=observed)
     try:
         cb = HipCallbacks(source, n_dim, n_derived=n_derived, **data_kwargs, **hipcallbacks_kwargs)
     except Exception as e:
@@ -1415,6 +1653,10 @@ def trace_callbacks(prior_transform, log_likelihood, n_dim, derived=None, check=
                        "probe": None}
     if data is not None:
         cb.trace_report["reads"] = {k: {name: sorted(how) for name, how in g.reads.items()} for k, g in graphs.items()}
+    if replicate is not None:
+        g = graphs["replicate"]
+        cb.trace_report["draws"] = {"replicate": {kind: sorted(g.nodes[i][1] for i in g.live() if g.nodes[i][0] == "noise_" + kind)
+                                                  for kind in ("normal", "uniform")}}
     if check:
-        cb.trace_report["probe"] = probe(cb, prior_transform, log_likelihood, derived, predict)
+        cb.trace_report["probe"] = probe(cb, prior_transform, log_likelihood, derived, predict, replicate, discrepancy)
     return cb

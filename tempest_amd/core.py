@@ -391,76 +391,58 @@ class SamplerCore:
             sel = ctx.compact_indices(w_dev, thr_dev[0:1], m_sel)
         return sel, m_sel, wdiv
 
-    def compute_predictive(self, quantiles=(0.025, 0.5, 0.975), trim_importance_weights=True, ess_trim=0.99, bins_trim=1000):
-        """Posterior predictive mean, variance and quantiles of the HipCallbacks source's predict(x, r) over the rows and weights
-        compute_posterior returns (same selection, on the device): the rows are gathered and reduced there, only the
-        (n_predict,) results reach the host."""
+    def _hip_owner(self, what, has, needs):
+        """The HipCallbacks object the likelihood belongs to, with the optional part Sampler.`what` reduces over: refused otherwise."""
         from ._lib import TempestHipError
         from .hipcallbacks import HipCallbacks
         owner = getattr(self.config.log_likelihood, "__self__", None)
-        if not isinstance(owner, HipCallbacks) or not owner.n_predict:
-            raise TempestHipError("Sampler.predictive: the likelihood is no HipCallbacks source that defines predict(...) (give it and n_predict=)")
+        if not isinstance(owner, HipCallbacks) or not getattr(owner, has):
+            raise TempestHipError(f"Sampler.{what}: the likelihood is no HipCallbacks source {needs}")
+        return owner
+
+    def _weighted_rows(self, what, unbuilt, trim_importance_weights, ess_trim, bins_trim, owner=None):
+        """(x_dev, w_sel): the rows and weights compute_posterior returns (same selection and row order), left on the device -- for
+        `owner`, a HipCallbacks object, on its device.  One shard only: Sampler.`what` needs `unbuilt` to fold the ranks' parts."""
         st = self.state
         if st.comm is not None and st.comm.active:
-            raise NotImplementedError("Sampler.predictive is not available on a sharded run yet: every rank holds a part of the rows, and "
-                                      "folding per-rank partial sums and bucket totals is not built (DESIGN.md section 10)")
+            raise NotImplementedError(f"Sampler.{what} is not available on a sharded run yet: every rank holds a part of the rows, and "
+                                      f"{unbuilt} (DESIGN.md section 10)")
         ctx = st.ctx
         ctx.use_current_stream()
-        if owner.device is None:
+        if owner is not None and owner.device is None:
             owner.device = st.device
         m, s1, _ = st.reweight_eval([1.0])[0]
         w_dev = ctx.weights(1.0, m, s1)
         sel, m_sel, wdiv = self._select_rows(w_dev, trim_importance_weights, ess_trim, bins_trim)
         x_dev, _, w_sel = ctx.posterior_rows(sel, m_sel, w=w_dev, wdiv=wdiv)
+        return x_dev, w_sel
+
+    def compute_predictive(self, quantiles=(0.025, 0.5, 0.975), trim_importance_weights=True, ess_trim=0.99, bins_trim=1000):
+        """Posterior predictive mean, variance and quantiles of the HipCallbacks source's predict(x, r) over the rows and weights
+        compute_posterior returns (same selection, on the device): the rows are gathered and reduced there, only the
+        (n_predict,) results reach the host."""
+        owner = self._hip_owner("predictive", "n_predict", "that defines predict(...) (give it and n_predict=)")
+        x_dev, w_sel = self._weighted_rows("predictive", "folding per-rank partial sums and bucket totals is not built",
+                                           trim_importance_weights, ess_trim, bins_trim, owner)
         return owner.predictive(x_dev, w_sel, quantiles)
 
     def compute_replicated(self, quantiles=(0.025, 0.5, 0.975), seed=None, trim_importance_weights=True, ess_trim=0.99, bins_trim=1000):
         """Replicated-data bands, PIT and Bayesian p-value of the HipCallbacks source's replicate(x, r, g) over the rows and weights
         compute_posterior returns (same selection and row order, on the device): the rows are gathered and reduced there, only the
         (n_replicate,) results reach the host.  seed None: the run's seed."""
-        from ._lib import TempestHipError
-        from .hipcallbacks import HipCallbacks
-        owner = getattr(self.config.log_likelihood, "__self__", None)
-        if not isinstance(owner, HipCallbacks) or not owner.n_replicate:
-            raise TempestHipError("Sampler.replicated: the likelihood is no HipCallbacks source that defines replicate(...) (give it and "
-                                  "n_replicate=)")
-        st = self.state
-        if st.comm is not None and st.comm.active:
-            raise NotImplementedError("Sampler.replicated is not available on a sharded run yet: every rank holds a part of the rows, and "
-                                      "a global row index for the draws and folding per-rank sums and counts are not built (DESIGN.md "
-                                      "section 10)")
-        ctx = st.ctx
-        ctx.use_current_stream()
-        if owner.device is None:
-            owner.device = st.device
-        m, s1, _ = st.reweight_eval([1.0])[0]
-        w_dev = ctx.weights(1.0, m, s1)
-        sel, m_sel, wdiv = self._select_rows(w_dev, trim_importance_weights, ess_trim, bins_trim)
-        x_dev, _, w_sel = ctx.posterior_rows(sel, m_sel, w=w_dev, wdiv=wdiv)
+        owner = self._hip_owner("replicated", "n_replicate", "that defines replicate(...) (give it and n_replicate=)")
+        x_dev, w_sel = self._weighted_rows("replicated", "a global row index for the draws and folding per-rank sums and counts are not built",
+                                           trim_importance_weights, ess_trim, bins_trim, owner)
         return owner.replicated(x_dev, w_sel, quantiles, seed=self.rng.seed if seed is None else seed)
 
     def compute_pointwise(self, trim_importance_weights=True, ess_trim=0.99, bins_trim=1000):
         """Pointwise log predictive densities, WAIC and importance-sampling LOO of a pointwise-enabled HipCallbacks source over the
         rows and weights compute_posterior returns (same selection, on the device): the rows are gathered and reduced there, only
         the (n_terms,) results reach the host."""
-        from ._lib import TempestHipError
-        from .hipcallbacks import HipCallbacks
-        owner = getattr(self.config.log_likelihood, "__self__", None)
-        if not isinstance(owner, HipCallbacks) or not owner.pointwise_enabled:
-            raise TempestHipError("Sampler.pointwise: the likelihood is no HipCallbacks source built with pointwise=True (give it, with a "
-                                  "source that defines log_likelihood_term)")
-        st = self.state
-        if st.comm is not None and st.comm.active:
-            raise NotImplementedError("Sampler.pointwise is not available on a sharded run yet: every rank holds a part of the rows, and "
-                                      "folding per-rank maxima, minima and partial sums is not built (DESIGN.md section 10)")
-        ctx = st.ctx
-        ctx.use_current_stream()
-        if owner.device is None:
-            owner.device = st.device
-        m, s1, _ = st.reweight_eval([1.0])[0]
-        w_dev = ctx.weights(1.0, m, s1)
-        sel, m_sel, wdiv = self._select_rows(w_dev, trim_importance_weights, ess_trim, bins_trim)
-        x_dev, _, w_sel = ctx.posterior_rows(sel, m_sel, w=w_dev, wdiv=wdiv)
+        owner = self._hip_owner("pointwise", "pointwise_enabled",
+                                "built with pointwise=True (give it, with a source that defines log_likelihood_term)")
+        x_dev, w_sel = self._weighted_rows("pointwise", "folding per-rank maxima, minima and partial sums is not built",
+                                           trim_importance_weights, ess_trim, bins_trim, owner)
         return owner.pointwise(x_dev, w_sel)
 
     def compute_marginals(self, bins=64, range=None, quantiles=(0.025, 0.16, 0.5, 0.84, 0.975), pairs=None, bins_2d=32, derived=True,
@@ -470,16 +452,8 @@ class SamplerCore:
         only per-column arrays and the tables reach the host (HipContext.marginals)."""
         import torch
         from .hipcallbacks import HipCallbacks
-        st = self.state
-        if st.comm is not None and st.comm.active:
-            raise NotImplementedError("Sampler.marginals is not available on a sharded run yet: every rank holds a part of the rows, and "
-                                      "folding per-rank minima, maxima, block sums and tables is not built (DESIGN.md section 10)")
-        ctx = st.ctx
-        ctx.use_current_stream()
-        m, s1, _ = st.reweight_eval([1.0])[0]
-        w_dev = ctx.weights(1.0, m, s1)
-        sel, m_sel, wdiv = self._select_rows(w_dev, trim_importance_weights, ess_trim, bins_trim)
-        x_dev, _, w_sel = ctx.posterior_rows(sel, m_sel, w=w_dev, wdiv=wdiv)
+        x_dev, w_sel = self._weighted_rows("marginals", "folding per-rank minima, maxima, block sums and tables is not built",
+                                           trim_importance_weights, ess_trim, bins_trim)
         n_dim, n_derived = x_dev.shape[1], 0
         fn = self.config.derived if derived else None
         owner = getattr(self.config.log_likelihood, "__self__", None)
@@ -488,14 +462,14 @@ class SamplerCore:
         if fn is not None:
             if isinstance(getattr(fn, "__self__", None), HipCallbacks):      # evaluated where the rows are
                 if fn.__self__.device is None:
-                    fn.__self__.device = st.device
+                    fn.__self__.device = self.state.device
                 extra = fn(x_dev)
             else:                                                            # a host function: its (M, k) block is uploaded
                 extra = torch.from_numpy(self._derived_fn()(x_dev)).to(x_dev.device)
             extra = extra.to(torch.float64).reshape(x_dev.shape[0], -1)
             n_derived = extra.shape[1]
             x_dev = torch.cat([x_dev, extra], dim=1).contiguous()
-        out = ctx.marginals(x_dev, w_sel, bins=bins, range=range, quantiles=quantiles, pairs=pairs, bins_2d=bins_2d)
+        out = self.state.ctx.marginals(x_dev, w_sel, bins=bins, range=range, quantiles=quantiles, pairs=pairs, bins_2d=bins_2d)
         out.update(n_dim=int(n_dim), n_derived=int(n_derived))
         return out
 

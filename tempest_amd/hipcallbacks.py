@@ -24,6 +24,7 @@ tempest_amd/_plugins/ when writable, else ~/.cache/tempest_amd/plugins).  The re
 callbacks are Python functions evaluated on the host (mcmc.py:152-160, core.py:317-358).
 """
 import ctypes as C
+from collections import namedtuple
 import hashlib
 import keyword
 import os
@@ -125,66 +126,63 @@ def derived_tiles(n_dim: int, n_derived: int):
     return tuple(r for r in DERIVED_TILES if r * ((n_dim | 1) + (n_derived | 1)) * 8 <= DERIVED_LDS_BYTES)
 
 
-def _has_derived(source: str) -> bool:
-    """The source DEFINES derived (`void derived(`): the word alone, in a comment or a name, is not a definition."""
-    return re.search(r"\bvoid\s+derived\s*\(", source) is not None
+# the optional callbacks of a source: what defines one, and what its extent argument n_<name>= is
+_OPTIONAL = {"derived": ("void derived(const double* x, double* out)", "how many values it writes"),
+             "predict": ("double predict(const double* x, int64_t r)", "an int, or the name of a data entry"),
+             "replicate": ("double replicate(const double* x, int64_t r, const tphu_noise& g)", "an int, or the name of a data entry"),
+             "discrepancy": ("double discrepancy(const double* x, int64_t r, double y)", None)}
 
 
-def _has_predict(source: str) -> bool:
-    """The source DEFINES predict (`double predict(`): the word alone, in a comment or a name, is not a definition."""
-    return re.search(r"\bdouble\s+predict\s*\(", source) is not None
+def _defines(source: str, name: str) -> bool:
+    """The source DEFINES the optional callback `name` (`void derived(`, `double predict(`, ...): the word alone, in a comment or a
+    name, is not a definition."""
+    return re.search(rf"\b{_OPTIONAL[name][0].split()[0]}\s+{name}\s*\(", source) is not None
 
 
-def _check_n_predict(source, n_predict, host) -> int:
-    has = _has_predict(source)
-    if n_predict is None:
-        if has:
-            raise ValueError("HipCallbacks: the source defines predict(...): give n_predict= (an int, or the name of a data entry)")
+def _defined_and_given(source: str, name: str, given) -> bool:
+    """_defines, for a callback that goes with an argument n_<name>=: one without the other is refused."""
+    has = _defines(source, name)
+    if has and given is None:
+        raise ValueError(f"HipCallbacks: the source defines {name}(...): give n_{name}= ({_OPTIONAL[name][1]})")
+    if given is not None and not has:
+        raise ValueError(f"HipCallbacks: n_{name}= goes with a source that defines __device__ {_OPTIONAL[name][0]}")
+    return has
+
+
+def _extent(v, what, host, prefix="HipCallbacks", below=None, of_an_entry=False) -> int:
+    """`what`= as an extent: the name of a data entry (its length, or its rows), or a positive int [below `below`] [that some entry
+    has as that extent]."""
+    if isinstance(v, str):
+        if v not in host:
+            raise ValueError(f"{prefix}: {what}={v!r} names no data entry")
+        return int(host[v].shape[0])
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) <= 0 or (below is not None and int(v) >= below):
+        raise ValueError(f"{prefix}: {what} must be a positive int or the name of a data entry, got {v!r}")
+    if of_an_entry and not any(a.shape[0] == int(v) for a in host.values()):
+        raise ValueError(f"{prefix}: {what}={int(v)} is the length (or the number of rows) of no data entry: the traced function "
+                         "has nothing to read per term")
+    return int(v)
+
+
+def _check_n_derived(source, n_derived) -> int:
+    if not _defined_and_given(source, "derived", n_derived):
         return 0
-    if not has:
-        raise ValueError("HipCallbacks: n_predict= goes with a source that defines __device__ double predict(const double* x, int64_t r)")
-    if isinstance(n_predict, str):
-        if n_predict not in host:
-            raise ValueError(f"HipCallbacks: n_predict={n_predict!r} names no data entry")
-        return int(host[n_predict].shape[0])
-    if isinstance(n_predict, bool) or not isinstance(n_predict, (int, np.integer)) or not 0 < int(n_predict) < 2 ** 31:
-        raise ValueError(f"HipCallbacks: n_predict must be a positive int or the name of a data entry, got {n_predict!r}")
-    return int(n_predict)
-
-
-def _has_replicate(source: str) -> bool:
-    """The source DEFINES replicate (`double replicate(`): the word alone, in a comment or a name, is not a definition."""
-    return re.search(r"\bdouble\s+replicate\s*\(", source) is not None
-
-
-def _has_discrepancy(source: str) -> bool:
-    """The source DEFINES discrepancy (`double discrepancy(`)."""
-    return re.search(r"\bdouble\s+discrepancy\s*\(", source) is not None
+    if isinstance(n_derived, bool) or not isinstance(n_derived, (int, np.integer)) or not 0 < int(n_derived) <= MAX_DERIVED:
+        raise ValueError(f"HipCallbacks: n_derived must be a positive int, at most {MAX_DERIVED}, got {n_derived!r}")
+    return int(n_derived)
 
 
 def _check_n_replicate(source, n_replicate, observed, host):
     """(n_replicate, name of the observed entry or None, the source has discrepancy()) of a checked HipCallbacks(n_replicate=, observed=)."""
-    has, disc = _has_replicate(source), _has_discrepancy(source)
-    if n_replicate is None:
-        if has:
-            raise ValueError("HipCallbacks: the source defines replicate(...): give n_replicate= (an int, or the name of a data entry)")
+    disc = _defines(source, "discrepancy")
+    if not _defined_and_given(source, "replicate", n_replicate):
         if observed is not None:
             raise ValueError("HipCallbacks: observed= goes with a source that defines replicate(...) (and n_replicate=)")
         if disc:
             raise ValueError("HipCallbacks: the source defines discrepancy(...): it goes with a source that defines replicate(...) "
                              "(and n_replicate=, observed=)")
         return 0, None, False
-    if not has:
-        raise ValueError("HipCallbacks: n_replicate= goes with a source that defines __device__ double replicate(const double* x, int64_t r, "
-                         "const tphu_noise& g)")
-    if isinstance(n_replicate, str):
-        if n_replicate not in host:
-            raise ValueError(f"HipCallbacks: n_replicate={n_replicate!r} names no data entry")
-        n_rep = int(host[n_replicate].shape[0])
-    elif isinstance(n_replicate, bool) or not isinstance(n_replicate, (int, np.integer)) or not 0 < int(n_replicate) < 2 ** 31:
-        raise ValueError(f"HipCallbacks: n_replicate must be a positive int or the name of a data entry, got {n_replicate!r}")
-    else:
-        n_rep = int(n_replicate)
+    n_rep = _extent(n_replicate, "n_replicate", host, below=2 ** 31)
     if observed is not None:
         if not isinstance(observed, str) or observed not in host:
             raise ValueError(f"HipCallbacks: observed={observed!r} names no data entry")
@@ -196,19 +194,23 @@ def _check_n_replicate(source, n_replicate, observed, host):
     return n_rep, observed, disc
 
 
+def _row_blocks(n: int) -> int:
+    """Blocks of PREDICT_SUM_LAYOUT[0] x PREDICT_SUM_LAYOUT[1] consecutive rows that n rows make."""
+    return -(-n // (PREDICT_SUM_LAYOUT[0] * PREDICT_SUM_LAYOUT[1]))
+
+
 def replicate_scratch_words(n: int, n_replicate: int, n_q: int) -> int:
     """8-byte words of scratch tphu_replicated gets for this call: W, the block sums of w, sum k, the p-value count, the PIT counters,
     the chunk and block sums of u T, and for a batch of indices what predictive() keeps -- all n_replicate indices, or as many as
     PREDICT_SCRATCH_WORDS hold."""
-    n_blocks = -(-n // (PREDICT_SUM_LAYOUT[0] * PREDICT_SUM_LAYOUT[1]))
+    n_blocks = _row_blocks(n)
     per_r = n_blocks + 258 * n_q + 1
     return 3 + 3 * n_blocks + 3 * n_replicate + 2 * -(-n // PREDICT_SUM_LAYOUT[0]) + per_r * min(n_replicate, max(1, PREDICT_SCRATCH_WORDS // per_r))
 
 
 def predict_tiles(n: int, n_predict: int, n_q: int):
     """(indices per workgroup, rows per workgroup of the select) predictive() launches with: the rule of PREDICT_MIN_WORKGROUPS."""
-    span = PREDICT_SUM_LAYOUT[0] * PREDICT_SUM_LAYOUT[1]
-    n_blocks = -(-n // span)
+    n_blocks = _row_blocks(n)
     tile = PREDICT_MAX_TILE
     while tile > 1 and n_blocks * -(-n_predict // tile) < PREDICT_MIN_WORKGROUPS:
         tile //= 2
@@ -220,14 +222,14 @@ def predict_tiles(n: int, n_predict: int, n_q: int):
 def predict_scratch_words(n: int, n_predict: int, n_q: int) -> int:
     """8-byte words of scratch tphu_predictive gets for this call: W and the block sums of w, and for a batch of indices the block
     sums, bucket totals, prefixes, targets and NaN flags -- all n_predict indices, or as many as PREDICT_SCRATCH_WORDS hold."""
-    n_blocks = -(-n // (PREDICT_SUM_LAYOUT[0] * PREDICT_SUM_LAYOUT[1]))
+    n_blocks = _row_blocks(n)
     per_r = n_blocks + 258 * n_q + 1
     return 1 + n_blocks + per_r * min(n_predict, max(1, PREDICT_SCRATCH_WORDS // per_r))
 
 
 def pointwise_tiles(n: int, n_terms: int) -> int:
     """Indices per workgroup pointwise() launches with: the rule of POINTWISE_MIN_WORKGROUPS."""
-    n_blocks = -(-n // (PREDICT_SUM_LAYOUT[0] * PREDICT_SUM_LAYOUT[1]))
+    n_blocks = _row_blocks(n)
     tile = POINTWISE_MAX_TILE
     while tile > 1 and n_blocks * -(-n_terms // tile) < POINTWISE_MIN_WORKGROUPS:
         tile //= 2
@@ -237,22 +239,17 @@ def pointwise_tiles(n: int, n_terms: int) -> int:
 def pointwise_scratch_words(n: int, n_terms: int) -> int:
     """8-byte words of scratch tphu_pointwise gets for this call: W and the block sums of w, and for a batch of indices four arrays
     of block values and the two shifts -- all n_terms indices, or as many as POINTWISE_SCRATCH_WORDS hold."""
-    n_blocks = -(-n // (PREDICT_SUM_LAYOUT[0] * PREDICT_SUM_LAYOUT[1]))
+    n_blocks = _row_blocks(n)
     per_r = 4 * n_blocks + 2
     return 1 + n_blocks + per_r * min(n_terms, max(1, POINTWISE_SCRATCH_WORDS // per_r))
 
 
-def _check_n_derived(source, n_derived) -> int:
-    has = _has_derived(source)
-    if n_derived is None:
-        if has:
-            raise ValueError("HipCallbacks: the source defines derived(...): give n_derived= (how many values it writes)")
-        return 0
-    if not has:
-        raise ValueError("HipCallbacks: n_derived= goes with a source that defines __device__ void derived(const double* x, double* out)")
-    if isinstance(n_derived, bool) or not isinstance(n_derived, (int, np.integer)) or not 0 < int(n_derived) <= MAX_DERIVED:
-        raise ValueError(f"HipCallbacks: n_derived must be a positive int, at most {MAX_DERIVED}, got {n_derived!r}")
-    return int(n_derived)
+def _quantiles(quantiles, what):
+    """The quantile levels of predictive() / replicated() as a checked float64 array."""
+    qs = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
+    if qs.ndim != 1 or len(qs) > MAX_QUANTILES or not np.all((qs >= 0.0) & (qs <= 1.0)):
+        raise ValueError(f"{what}: quantiles must be at most {MAX_QUANTILES} numbers in [0, 1], got {quantiles!r}")
+    return qs
 
 
 def _table_spec(data):
@@ -315,45 +312,132 @@ def _struct_text(tables) -> str:
     return "\n".join(lines)
 
 
+_PTR, _I64, _INT = C.c_void_p, C.c_int64, C.c_int
+_PREDICT_LAYOUT = PREDICT_SUM_LAYOUT + (PREDICT_MAX_TILE, PREDICT_TABLES)
+
+
+# One optional part of a plugin -- everything the host knows about it; a new part is a new row of _PARTS and a field of _Parts.
+# name: the field of _Parts that says whether a plugin has it; mark: its lines of the template, dropped whole without it; define, word:
+# what it adds to the compiler's command line and to the cache key -- present only with the part, so every other source keeps its file
+# name; entry, argtypes: its entry point (a data-carrying plugin takes tphu_data last); report, layout, mismatch: the handshake --
+# tphu_*_layout(i), or one exported function per figure, the tuple they must return [as a function of (n_dim, parts)], and what
+# "does / do not match this package" otherwise.
+_Part = namedtuple("_Part", "name mark define word entry argtypes report layout mismatch", defaults=(None, (), None, None, None))
+_PARTS = (
+    _Part("term", "//@T", None, "", "tphu_like_split", (_PTR, _PTR, _I64, _I64, _PTR, _PTR, _I64, _INT)),
+    _Part("n_derived", "//@X", "-DN_DERIVED={n_derived}", "|derived={n_derived}", "tphu_derived", (_PTR, _PTR, _I64, _I64, _PTR, _I64, _INT, _INT),
+          ("tphu_n_derived", "tphu_derived_rows"), lambda n_dim, p: (p.n_derived, (derived_tiles(n_dim, p.n_derived) or (0,))[0]),
+          "derived() shape or tile rule does"),
+    _Part("predict", "//@P", "-DTPHU_PREDICT", "|predict", "tphu_predictive",
+          (_PTR, _PTR, _PTR, _I64, _I64, _PTR, _INT, _PTR, _PTR, _I64, _INT, _I64),
+          "tphu_predict_layout", _PREDICT_LAYOUT, "predict() sum layout or tile limits do"),
+    _Part("pointwise", "//@W", "-DTPHU_POINTWISE", "|pointwise", "tphu_pointwise", (_PTR, _PTR, _PTR, _I64, _I64, _PTR, _PTR, _I64, _INT),
+          "tphu_pointwise_layout", PREDICT_SUM_LAYOUT + (POINTWISE_MAX_TILE,), "pointwise sum layout or tile limit does"),
+    _Part("replicate", "//@Y", "-DTPHU_REPLICATE", "|replicate", "tphu_replicated",
+          (_PTR, _PTR, _PTR, _I64, _I64, _PTR, _INT, C.c_uint64, _PTR, _INT, _PTR, _PTR, _I64, _INT, _I64),
+          "tphu_replicate_layout", _PREDICT_LAYOUT + SUM_LAYOUT + REPLICATE_TAGS, "replicate() sum layouts, tile limits or RNG tags do"),
+    _Part("discrepancy", None, "-DTPHU_DISCREPANCY", "|discrepancy"),
+)
+
+
+class _Parts(namedtuple("_Parts", "tables term n_derived predict pointwise replicate discrepancy traced",
+                        defaults=(None, False, 0, False, False, False, False, False))):
+    """What a plugin has beside the two callbacks of x: the record every difference between two plugins derives from -- the template
+    lines kept, the -D list, the words of the key, the entry points bound and the layouts checked.  tables None: callbacks of x alone
+    (the template as it always was, byte for byte); ((name, rank), ...): the callbacks take `const tphu_data& D` and every kernel and
+    entry point carries the table; term: the source gives log_likelihood_term and the library owns the sum; n_derived > 0: it gives
+    derived(x, out) (k_user_derived / tphu_derived); predict: predict(x, r) (the k_user_predict_* kernels / tphu_predictive);
+    pointwise (term form only): the k_user_pw_* kernels / tphu_pointwise; replicate: replicate(x, r, g) (tphu_noise, the k_user_rep_*
+    kernels / tphu_replicated), with discrepancy where the source also gives discrepancy(); traced: the source calls the helpers of
+    tempest_amd.trace (tphu_tr_max / tphu_tr_min)."""
+    __slots__ = ()
+
+    @classmethod
+    def of(cls, source, tables=None, term=False, n_derived=0, predict=False, pointwise=False, replicate=False, discrepancy=False):
+        return cls(() if term and tables is None else tables, bool(term), max(0, int(n_derived)), bool(predict), bool(pointwise),
+                   bool(replicate), bool(replicate and discrepancy), re.search(r"\btphu_tr_(max|min)\s*\(", source) is not None)
+
+    def build_args(self) -> dict:          # the keyword arguments of build_plugin that give this record back
+        return {k: v for k, v in self._asdict().items() if k != "traced"}
+
+    def present(self):
+        return [part for part in _PARTS if getattr(self, part.name)]
+
+    def text(self, source: str) -> str:
+        """The translation unit for `source`."""
+        # lines of one part only are dropped whole without it; //@D: the data form; //@Q: what predict, pointwise and replicate share --
+        # the layout constants, the row loads, the sum of the weights; //@S: what predict and replicate share -- the fold of the block
+        # sums, the select's key and its narrowing kernel; //@R: the helpers a traced source calls
+        rows = self.predict or self.pointwise or self.replicate
+        keep = {"//@D": self.tables is not None, "//@S": self.predict or self.replicate, "//@Q": rows, "//@R": self.traced}
+        keep.update((part.mark, bool(getattr(self, part.name))) for part in _PARTS if part.mark)
+        out = []
+        for line in _TEMPLATE.read_text().split("\n"):
+            if line[:4] in keep and line[4:5] in ("", " "):
+                if keep[line[:4]]:
+                    out.append(line[5:])
+            else:
+                out.append(line)
+        text = "\n".join(out)
+        on = self.tables is not None
+        for mark, val in (("@D_PARAM@", ", const tphu_data D"), ("@D_REF@", ", const tphu_data& Dt"), ("@D_TARG@", ", Dt"), ("@D_ARG@", ", D"),
+                          ("@D_HOST@", ", const tphu_data* Dh"), ("@D_LAUNCH@", ", *Dh"), ("@D_KARG@", ", (void*)Dh"),
+                          ("@D_NONNULL@", " && Dh")):
+            text = text.replace(mark, val if on else "")
+        if on:
+            text = text.replace("@DATA_STRUCT@", _struct_text(self.tables))
+        if self.term or self.replicate:
+            text = text.replace("@TPHU_CHUNK@", str(SUM_LAYOUT[0])).replace("@TPHU_BLOCK@", str(SUM_LAYOUT[1]))
+        if rows:
+            text = text.replace("@TPHU_PCHUNK@", str(PREDICT_SUM_LAYOUT[0])).replace("@TPHU_PBLOCK@", str(PREDICT_SUM_LAYOUT[1]))
+        return text.replace("@USER_SOURCE@", source)
+
+    def defines(self, n_dim: int):
+        return [f"-DN_DIM={int(n_dim)}"] + [part.define.format(**self._asdict()) for part in self.present() if part.define]
+
+    def key(self, n_dim: int) -> str:
+        """What build_plugin hashes beside the text and the headers: dimension, architecture, flags, toolchain, a word per part."""
+        return f"|{n_dim}|{_ARCH}|{' '.join(_FLAGS)}|{_toolchain_id()}" + "".join(part.word.format(**self._asdict()) for part in self.present())
+
+    def bind(self, lib, n_dim: int, path):
+        """Declare the entry points of the loaded plugin and check that it was built for this package's layouts; returns the
+        ctypes type of tphu_data (None without tables)."""
+        lib.tphu_last_error.restype = C.c_char_p
+        u32, dbl = C.c_uint32, C.c_double
+        fns = {"tphu_prior": (_PTR, _PTR, _I64, _I64, _PTR, _I64), "tphu_like": (_PTR, _PTR, _I64, _I64, _PTR),
+               "tphu_accept": (_PTR, _INT, dbl, _PTR, _PTR, _PTR, _PTR, _PTR, _PTR, _PTR, _I64, _I64, _INT, _PTR, C.c_uint64, u32, _I64,
+                               _PTR, _PTR, _PTR, _PTR),
+               "tphu_step": (_PTR, _INT, dbl, _PTR, _PTR, _PTR, _I64, _I64, _PTR, _PTR, _PTR, _PTR, _PTR, _PTR, C.c_uint64, u32, u32, _I64,
+                             _PTR, _PTR, _INT),
+               "tphu_run": (_PTR, _INT, _PTR, _PTR, _PTR, _I64, _I64, _PTR, _PTR, _PTR, _PTR, _PTR, _PTR, C.c_uint64, u32, u32, _I64, _PTR,
+                            _PTR, _PTR, _PTR, dbl, _INT, _INT, _PTR, _INT, _INT, _INT, _INT)}
+        fns.update((part.entry, part.argtypes) for part in self.present() if part.entry)
+        struct = None
+        if self.tables is not None:            # a data-carrying plugin: every entry point takes the host copy of tphu_data last
+            fields = [f for name, rank in self.tables for f in
+                      [(name, _PTR)] + ([(name + "_len", _I64)] if rank == 1 else [(name + "_rows", _I64), (name + "_cols", _I64)])]
+            struct = type("tphu_data", (C.Structure,), {"_fields_": fields + [("n_terms", _I64)]})
+            if lib.tphu_data_abi() != 1 or lib.tphu_data_size() != C.sizeof(struct):
+                raise TempestHipError(f"plugin {path}: data table layout does not match this package")
+        for name, argtypes in fns.items():
+            fn = getattr(lib, name)
+            fn.argtypes, fn.restype = list(argtypes) + ([_PTR] if struct is not None else []), _INT
+        if lib.tphu_n_dim() != n_dim:
+            raise TempestHipError(f"plugin {path} was built for n_dim={lib.tphu_n_dim()}")
+        for part in self.present():            # every exported figure is an int, ctypes' default
+            if part.report is not None:
+                want = part.layout(n_dim, self) if callable(part.layout) else part.layout
+                got = tuple(getattr(lib, part.report)(i) for i in range(len(want))) if isinstance(part.report, str) \
+                    else tuple(getattr(lib, name)() for name in part.report)
+                if got != want:
+                    raise TempestHipError(f"plugin {path}: {part.mismatch} not match this package")
+        return struct
+
+
 def plugin_source(source: str, tables=None, term: bool = False, *, derived: bool = False, predict: bool = False,
                   pointwise: bool = False, replicate: bool = False) -> str:
-    """The translation unit for `source`.  tables None: callbacks of x alone (the template as it always was, byte for byte);
-    ((name, rank), ...): the callbacks take `const tphu_data& D` and every kernel and entry point carries the table;
-    term: the source gives log_likelihood_term and the library owns the sum; derived: the source gives derived(x, out) and the
-    plugin gets k_user_derived / tphu_derived (compiled with -DN_DERIVED=k); predict: the source gives predict(x, r) and the plugin
-    gets the k_user_predict_* kernels / tphu_predictive (compiled with -DTPHU_PREDICT); pointwise (term form only): the plugin gets
-    the k_user_pw_* kernels / tphu_pointwise (compiled with -DTPHU_POINTWISE); replicate: the source gives replicate(x, r, g) and the
-    plugin gets tphu_noise, the k_user_rep_* kernels / tphu_replicated (compiled with -DTPHU_REPLICATE, and -DTPHU_DISCREPANCY where
-    the source also gives discrepancy())."""
-    text = _TEMPLATE.read_text()
-    if term and tables is None:
-        tables = ()
-    # lines of the data / term form / a source with derived() / with predict() / with pointwise=True only: dropped whole otherwise
-    # (//@Q: what predict and pointwise share -- the layout constants, the row loads, the sum of the weights; //@R: the helpers a
-    # traced source calls, tempest_amd.trace; //@Y: a source with replicate(); //@S: what predict and replicate share -- the fold of
-    # the block sums, the select's key and its narrowing kernel)
-    keep = {"//@D": tables is not None, "//@T": term, "//@X": derived, "//@P": predict, "//@W": pointwise, "//@Y": replicate,
-            "//@S": predict or replicate, "//@Q": predict or pointwise or replicate, "//@R": re.search(r"\btphu_tr_(max|min)\s*\(", source) is not None}
-    out = []
-    for line in text.split("\n"):
-        if line[:4] in keep and line[4:5] in ("", " "):
-            if keep[line[:4]]:
-                out.append(line[5:])
-        else:
-            out.append(line)
-    text = "\n".join(out)
-    on = tables is not None
-    for mark, val in (("@D_PARAM@", ", const tphu_data D"), ("@D_REF@", ", const tphu_data& Dt"), ("@D_TARG@", ", Dt"), ("@D_ARG@", ", D"),
-                      ("@D_HOST@", ", const tphu_data* Dh"), ("@D_LAUNCH@", ", *Dh"), ("@D_KARG@", ", (void*)Dh"),
-                      ("@D_NONNULL@", " && Dh")):
-        text = text.replace(mark, val if on else "")
-    if on:
-        text = text.replace("@DATA_STRUCT@", _struct_text(tables))
-    if term or replicate:
-        text = text.replace("@TPHU_CHUNK@", str(SUM_LAYOUT[0])).replace("@TPHU_BLOCK@", str(SUM_LAYOUT[1]))
-    if predict or pointwise or replicate:
-        text = text.replace("@TPHU_PCHUNK@", str(PREDICT_SUM_LAYOUT[0])).replace("@TPHU_PBLOCK@", str(PREDICT_SUM_LAYOUT[1]))
-    return text.replace("@USER_SOURCE@", source)
+    """The translation unit for `source` with these parts (see _Parts)."""
+    return _Parts.of(source, tables, term, int(derived), predict, pointwise, replicate).text(source)
 
 
 _TOOLCHAIN = None
@@ -374,27 +458,19 @@ def _toolchain_id() -> str:
 
 def plugin_key(n_dim: int, *, n_derived: int = 0, predict: bool = False, pointwise: bool = False, replicate: bool = False,
                discrepancy: bool = False) -> str:
-    """What build_plugin hashes beside the text and the headers: dimension, architecture, flags, toolchain, and a word per optional
-    part -- present only where the source has that part, so every other source keeps the key it had."""
-    return f"|{n_dim}|{_ARCH}|{' '.join(_FLAGS)}|{_toolchain_id()}" + (f"|derived={int(n_derived)}" if n_derived > 0 else "") \
-        + ("|predict" if predict else "") + ("|pointwise" if pointwise else "") + ("|replicate" if replicate else "") \
-        + ("|discrepancy" if replicate and discrepancy else "")
+    """The cache key of a plugin with these parts beside the text and the headers (see _Parts.key)."""
+    return _Parts.of("", None, False, n_derived, predict, pointwise, replicate, discrepancy).key(n_dim)
 
 
 def build_plugin(source: str, n_dim: int, verbose: bool = False, tables=None, term: bool = False, *, n_derived: int = 0,
                  predict: bool = False, pointwise: bool = False, replicate: bool = False, discrepancy: bool = False) -> Path:
-    """Compile (or find in the cache) the plugin for `source`; returns the path of the shared library.  `tables` / `term` as in
-    plugin_source: names, ranks and the element type of the data entries are in the generated text and so in the key; values and
-    extents are not -- one compile serves every data set of that shape of table.  n_derived > 0: the source has derived(); only then
-    do -DN_DERIVED and its part of the key exist, so every other source keeps the file name it had; the same holds for predict
-    (the source has predict()): -DTPHU_PREDICT and "|predict" in the key only then; for pointwise (-DTPHU_POINTWISE, "|pointwise"); and for
-    replicate (the source has replicate(): -DTPHU_REPLICATE, "|replicate"; with discrepancy() too: -DTPHU_DISCREPANCY, "|discrepancy")."""
-    text = plugin_source(source, tables, term, derived=n_derived > 0, predict=predict, pointwise=pointwise, replicate=replicate)
-    defs = [f"-DN_DIM={int(n_dim)}"] + ([f"-DN_DERIVED={int(n_derived)}"] if n_derived > 0 else []) + (["-DTPHU_PREDICT"] if predict else []) \
-        + (["-DTPHU_POINTWISE"] if pointwise else []) + (["-DTPHU_REPLICATE"] if replicate else []) \
-        + (["-DTPHU_DISCREPANCY"] if replicate and discrepancy else [])
+    """Compile (or find in the cache) the plugin for `source`; returns the path of the shared library.  The arguments after
+    `verbose` are the fields of _Parts: names, ranks and the element type of the data entries are in the generated text and so in
+    the key; values and extents are not -- one compile serves every data set of that shape of table.  A -D and a word of the key exist
+    only with their part, so every other source keeps the file name it had."""
+    parts = _Parts.of(source, tables, term, n_derived, predict, pointwise, replicate, discrepancy)
+    text, defs, key = parts.text(source), parts.defines(n_dim), parts.key(n_dim)
     deps = (_CSRC / "common.h").read_bytes() + (_CSRC.parent.parent / "include" / "tempest_hip.h").read_bytes()
-    key = plugin_key(n_dim, n_derived=n_derived, predict=predict, pointwise=pointwise, replicate=replicate, discrepancy=discrepancy)
     tag = hashlib.sha256(text.encode() + deps + key.encode()).hexdigest()[:20]
     name = f"tphu_{n_dim}d_{tag}.so"
     for d in _cache_dirs():
@@ -424,13 +500,18 @@ def build_plugin(source: str, n_dim: int, verbose: bool = False, tables=None, te
 class HipCallbacks:
     """prior_transform + log_likelihood as HIP device functions (see the module docstring)."""
 
-    # a source of x alone: no tables, no term form (class defaults; __init__ fills them in where `data=` / `n_terms=` are given)
-    term, tables, n_terms, data_like, split_tile, sum_layout = False, None, 0, None, 0, SUM_LAYOUT
-    n_derived, derived_tile = 0, 0
+    # a source of x alone: no tables, no term form, no optional part (class defaults; __init__ fills in what its arguments give)
+    parts = _Parts()
+    term, tables, n_terms, sum_layout = False, None, 0, SUM_LAYOUT
+    data_like = None                       # "lane" | "split" pins a path of the term-form likelihood (TEMPEST_AMD_DATA_LIKE, read once)
+    split_tile = 0                         # > 0 pins the particles per workgroup of the split kernel (64, 16, 4, 1)
+    n_derived, derived_tile = 0, 0         # tile > 0 pins the row-major derived kernel: 256 / 128 / 64 rows per workgroup, 1 = direct
+    # tile > 0 pins the indices per workgroup of predictive() (1 .. 64); (tile, slab) also the rows per workgroup of its select
     n_predict, predict_tile, predict_sum_layout = 0, 0, PREDICT_SUM_LAYOUT
-    pointwise_enabled, pointwise_tile = False, 0
+    pointwise_enabled, pointwise_tile = False, 0      # tile > 0 pins the indices per workgroup of pointwise() (1 .. 64)
     n_replicate, observed, has_discrepancy = 0, None, False
-    _device = _dev_tables = _dstruct = _bsum = _pscratch = _wscratch = _yscratch = None
+    run_groups = 0                         # > 0 limits the workgroups of tphu_run's launch (tests: several tiles per workgroup)
+    _device = _dev_tables = _dstruct = _struct_type = _bsum = _pscratch = _wscratch = _yscratch = None
 
     def __init__(self, source: str, n_dim: int, fused: bool = True, verbose: bool = False, whole_step: bool = True,
                  persistent: bool = False, data=None, n_terms=None, n_derived=None, n_predict=None, *,
@@ -451,41 +532,17 @@ class HipCallbacks:
             raise ValueError(f"HipCallbacks: pointwise must be True or False, got {pointwise!r}")
         if pointwise and not has_term:
             raise ValueError("HipCallbacks: pointwise=True goes with a source that defines log_likelihood_term (and n_terms=)")
-        self.pointwise_enabled = bool(pointwise)
-        self.pointwise_tile = 0                # > 0 pins the indices per workgroup of pointwise() (1 .. 64)
-        self._wscratch = None
         self.n_derived = _check_n_derived(source, n_derived)
-        self.derived_tile = 0                  # > 0 pins the row-major derived kernel: 256 / 128 / 64 rows per workgroup, 1 = direct
-        self.term = has_term
-        self.tables, self._host = (None, {}) if data is None else _table_spec(data)
-        if has_term and self.tables is None:
-            self.tables = ()
-        self.n_predict = _check_n_predict(source, n_predict, self._host)
-        # > 0 pins the indices per workgroup of predictive() (1 .. 64); (tile, slab) also the rows per workgroup of its select
-        self.predict_tile = 0
-        self._pscratch = None
+        tables, self._host = (None, {}) if data is None else _table_spec(data)
+        if _defined_and_given(source, "predict", n_predict):
+            self.n_predict = _extent(n_predict, "n_predict", self._host, below=2 ** 31)
         self.n_replicate, self.observed, self.has_discrepancy = _check_n_replicate(source, n_replicate, observed, self._host)
-        self._yscratch = None
-        self.n_terms = 0
         if has_term:
-            if isinstance(n_terms, str):
-                if n_terms not in self._host:
-                    raise ValueError(f"HipCallbacks: n_terms={n_terms!r} names no data entry")
-                self._n_terms_of = n_terms
-                self.n_terms = int(self._host[n_terms].shape[0])
-            elif isinstance(n_terms, (int, np.integer)) and not isinstance(n_terms, bool) and int(n_terms) > 0:
-                self._n_terms_of = None
-                self.n_terms = int(n_terms)
-            else:
-                raise ValueError(f"HipCallbacks: n_terms must be a positive int or the name of a data entry, got {n_terms!r}")
-        self.sum_layout = SUM_LAYOUT
-        mode = os.environ.get("TEMPEST_AMD_DATA_LIKE", "").strip().lower()          # read once: lane | split pins a path
+            self.n_terms = _extent(n_terms, "n_terms", self._host)
+        mode = os.environ.get("TEMPEST_AMD_DATA_LIKE", "").strip().lower()
         if mode not in ("", "lane", "split"):
             raise ValueError(f"TEMPEST_AMD_DATA_LIKE must be 'lane' or 'split', got {mode!r}")
         self.data_like = mode or None
-        self.split_tile = 0                    # > 0 pins the particles per workgroup of the split kernel (64, 16, 4, 1)
-        self._device = None
-        self._dev_tables, self._dstruct, self._bsum = None, None, None
         self.n_dim, self.source, self.fused = n_dim, source, bool(fused)
         self.whole_step = whole_step           # False: proposal and evaluate+accept as two kernels; "always": at any size
         # A whole run of steps in ONE cooperative launch (tphu_run) where the whole-step kernel applies.  OFF by default: measured
@@ -495,69 +552,12 @@ class HipCallbacks:
         # TEMPEST_AMD_PERSISTENT=1/0 overrides the argument.
         env = os.environ.get("TEMPEST_AMD_PERSISTENT")
         self.persistent = bool(persistent) if env is None else env != "0"
-        self.run_groups = 0                    # > 0 limits the workgroups of that launch (tests: several tiles per workgroup)
-        self.path = build_plugin(source, n_dim, verbose, self.tables, self.term, n_derived=self.n_derived, predict=bool(self.n_predict),
-                                 pointwise=self.pointwise_enabled, replicate=bool(self.n_replicate), discrepancy=self.has_discrepancy)
+        self.parts = _Parts.of(source, tables, has_term, self.n_derived, self.n_predict, pointwise, self.n_replicate, self.has_discrepancy)
+        self.tables, self.term, self.pointwise_enabled = self.parts.tables, self.parts.term, self.parts.pointwise
+        self.path = build_plugin(source, n_dim, verbose, **self.parts.build_args())
         import torch  # noqa: F401  (its HIP runtime must be the one in the process, as for libtempest_hip)
-        lib = C.CDLL(str(self.path))
-        ptr, i64 = C.c_void_p, C.c_int64
-        lib.tphu_last_error.restype = C.c_char_p
-        lib.tphu_n_dim.restype = C.c_int
-        lib.tphu_prior.argtypes = [ptr, ptr, i64, i64, ptr, i64]
-        lib.tphu_like.argtypes = [ptr, ptr, i64, i64, ptr]
-        lib.tphu_accept.argtypes = [ptr, C.c_int, C.c_double, ptr, ptr, ptr, ptr, ptr, ptr, ptr, i64, i64, C.c_int, ptr,
-                                    C.c_uint64, C.c_uint32, i64, ptr, ptr, ptr, ptr]
-        lib.tphu_step.argtypes = [ptr, C.c_int, C.c_double, ptr, ptr, ptr, i64, i64, ptr, ptr, ptr, ptr, ptr, ptr, C.c_uint64,
-                                  C.c_uint32, C.c_uint32, i64, ptr, ptr, C.c_int]
-        lib.tphu_run.argtypes = [ptr, C.c_int, ptr, ptr, ptr, i64, i64, ptr, ptr, ptr, ptr, ptr, ptr, C.c_uint64, C.c_uint32, C.c_uint32,
-                                 i64, ptr, ptr, ptr, ptr, C.c_double, C.c_int, C.c_int, ptr, C.c_int, C.c_int, C.c_int, C.c_int]
-        fns = [lib.tphu_prior, lib.tphu_like, lib.tphu_accept, lib.tphu_step, lib.tphu_run]
-        if self.n_derived:
-            lib.tphu_derived.argtypes = [ptr, ptr, i64, i64, ptr, i64, C.c_int, C.c_int]
-            fns.append(lib.tphu_derived)
-            lib.tphu_n_derived.restype = lib.tphu_derived_rows.restype = C.c_int
-        if self.n_predict:
-            lib.tphu_predictive.argtypes = [ptr, ptr, ptr, i64, i64, ptr, C.c_int, ptr, ptr, i64, C.c_int, i64]
-            fns.append(lib.tphu_predictive)
-            lib.tphu_predict_layout.argtypes, lib.tphu_predict_layout.restype = [C.c_int], C.c_int
-        if self.pointwise_enabled:
-            lib.tphu_pointwise.argtypes = [ptr, ptr, ptr, i64, i64, ptr, ptr, i64, C.c_int]
-            fns.append(lib.tphu_pointwise)
-            lib.tphu_pointwise_layout.argtypes, lib.tphu_pointwise_layout.restype = [C.c_int], C.c_int
-        if self.n_replicate:
-            lib.tphu_replicated.argtypes = [ptr, ptr, ptr, i64, i64, ptr, C.c_int, C.c_uint64, ptr, C.c_int, ptr, ptr, i64, C.c_int, i64]
-            fns.append(lib.tphu_replicated)
-            lib.tphu_replicate_layout.argtypes, lib.tphu_replicate_layout.restype = [C.c_int], C.c_int
-        if self.tables is not None:            # a data-carrying plugin: every entry point takes the host copy of tphu_data last
-            for f in fns:
-                f.argtypes = list(f.argtypes) + [ptr]
-            fields = []
-            for name, rank in self.tables:
-                fields.append((name, ptr))
-                fields += [(name + "_len", i64)] if rank == 1 else [(name + "_rows", i64), (name + "_cols", i64)]
-            fields.append(("n_terms", i64))
-            self._struct_type = type("tphu_data", (C.Structure,), {"_fields_": fields})
-            lib.tphu_data_abi.restype = lib.tphu_data_size.restype = C.c_int
-            if lib.tphu_data_abi() != 1 or lib.tphu_data_size() != C.sizeof(self._struct_type):
-                raise TempestHipError(f"plugin {self.path}: data table layout does not match this package")
-        if self.term:
-            lib.tphu_like_split.argtypes = [ptr, ptr, i64, i64, ptr, ptr, i64, C.c_int, ptr]
-            fns.append(lib.tphu_like_split)
-        for f in fns:
-            f.restype = C.c_int
-        if lib.tphu_n_dim() != n_dim:
-            raise TempestHipError(f"plugin {self.path} was built for n_dim={lib.tphu_n_dim()}")
-        if self.n_derived and (lib.tphu_n_derived() != self.n_derived
-                               or lib.tphu_derived_rows() != (derived_tiles(n_dim, self.n_derived) or (0,))[0]):
-            raise TempestHipError(f"plugin {self.path}: derived() shape or tile rule does not match this package")
-        if self.n_predict and tuple(lib.tphu_predict_layout(i) for i in range(4)) != PREDICT_SUM_LAYOUT + (PREDICT_MAX_TILE, PREDICT_TABLES):
-            raise TempestHipError(f"plugin {self.path}: predict() sum layout or tile limits do not match this package")
-        if self.pointwise_enabled and tuple(lib.tphu_pointwise_layout(i) for i in range(3)) != PREDICT_SUM_LAYOUT + (POINTWISE_MAX_TILE,):
-            raise TempestHipError(f"plugin {self.path}: pointwise sum layout or tile limit does not match this package")
-        if self.n_replicate and tuple(lib.tphu_replicate_layout(i) for i in range(8)) != PREDICT_SUM_LAYOUT + (PREDICT_MAX_TILE, PREDICT_TABLES) \
-                + SUM_LAYOUT + REPLICATE_TAGS:
-            raise TempestHipError(f"plugin {self.path}: replicate() sum layouts, tile limits or RNG tags do not match this package")
-        self.lib = lib
+        self.lib = C.CDLL(str(self.path))
+        self._struct_type = self.parts.bind(self.lib, n_dim, self.path)
 
     # ---------------------------------------------------------------------------------- data tables
     @property
@@ -668,6 +668,32 @@ class HipCallbacks:
         t = a.T
         return (t if t.is_contiguous() else t.contiguous()), was_np, one
 
+    def _kept_scratch(self, attr, words, device):
+        """The buffer kept under `attr`, of at least `words` 8-byte words on `device`: grown on demand, no allocation per call."""
+        import torch
+        buf = getattr(self, attr)
+        if buf is None or buf.numel() < words or buf.device != device:
+            buf = torch.empty(words, dtype=torch.int64, device=device)
+            setattr(self, attr, buf)
+        return buf
+
+    def _on_device(self, a):
+        """A tensor or array as a contiguous float64 tensor on a device: host inputs go to `self.device` (the current one if None)."""
+        import torch
+        if not isinstance(a, torch.Tensor):
+            a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64))
+        if not a.is_cuda:
+            a = a.to(self._device or torch.device("cuda", torch.cuda.current_device()))
+        return a.to(torch.float64).contiguous()
+
+    def _predict_launch(self, n, R, nq):
+        """(indices per workgroup, rows per workgroup of the select) of predictive() / replicated(): predict_tiles, or the pin."""
+        tile, slab = predict_tiles(n, R, nq)
+        pin = self.predict_tile
+        if pin:
+            tile, slab = (int(pin[0]), int(pin[1])) if isinstance(pin, (tuple, list)) else (int(pin), slab)
+        return tile, slab
+
     # ---------------------------------------------------------------------------------- callbacks
     def prior_transform(self, u):
         """(n, n_dim) unit-cube points [or one point] -> parameters, same container kind as the input."""
@@ -688,10 +714,9 @@ class HipCallbacks:
         if self.use_split(n):
             span = self.sum_layout[0] * self.sum_layout[1]
             n_blocks = -(-self.n_terms // span)
-            if self._bsum is None or self._bsum.numel() < n * n_blocks or self._bsum.device != xs.device:
-                self._bsum = torch.empty(n * n_blocks, dtype=torch.float64, device=xs.device)   # kept: no allocation per call
-            self._check(self.lib.tphu_like_split(self._stream(xs), xs.data_ptr(), n, n, ll.data_ptr(), self._bsum.data_ptr(),
-                                                 self._bsum.numel(), self._tile(n, n_blocks), *self._data()), "tphu_like_split")
+            bsum = self._kept_scratch("_bsum", n * n_blocks, xs.device)
+            self._check(self.lib.tphu_like_split(self._stream(xs), xs.data_ptr(), n, n, ll.data_ptr(), bsum.data_ptr(),
+                                                 bsum.numel(), self._tile(n, n_blocks), *self._data()), "tphu_like_split")
         else:
             self._check(self.lib.tphu_like(self._stream(xs), xs.data_ptr(), n, n, ll.data_ptr(), *self._data()), "tphu_like")
         ll = ll[0] if one else ll
@@ -721,8 +746,7 @@ class HipCallbacks:
             was_np, one = not isinstance(x, torch.Tensor), False
             if was_np:
                 one = xa.ndim == 1
-                x = torch.from_numpy(np.ascontiguousarray(xa.reshape(-1, self.n_dim))).to(
-                    self._device or torch.device("cuda", torch.cuda.current_device()))
+                x = self._on_device(xa.reshape(-1, self.n_dim))
             if x.shape[1] != self.n_dim:
                 raise ValueError(f"expected (..., {self.n_dim}) points, got {tuple(x.shape)}")
             n = x.shape[0]
@@ -747,15 +771,7 @@ class HipCallbacks:
         """The (n, n_dim) points and (n,) weights of predictive() / pointwise() as contiguous float64 device tensors, checked: n > 0,
         weights finite, >= 0, with a positive sum.  Returns (x, w, n, sum w, sum w^2)."""
         import torch
-        dev = self._device or torch.device("cuda", torch.cuda.current_device())
-
-        def on_device(a):
-            if not isinstance(a, torch.Tensor):
-                a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64))
-            if not a.is_cuda:
-                a = a.to(dev)
-            return a.to(torch.float64).contiguous()
-        x, w = on_device(x), on_device(w)
+        x, w = self._on_device(x), self._on_device(w)
         if x.dim() != 2 or x.shape[1] != self.n_dim or x.shape[0] == 0:
             raise ValueError(f"{what}: expected (n, {self.n_dim}) points with n > 0, got {tuple(x.shape)}")
         n = x.shape[0]
@@ -777,22 +793,14 @@ class HipCallbacks:
         import torch
         if not self.n_predict:
             raise TempestHipError("HipCallbacks.predictive: the source defines no predict(...) (give it and n_predict=)")
-        qs = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
-        if qs.ndim != 1 or len(qs) > MAX_QUANTILES or not np.all((qs >= 0.0) & (qs <= 1.0)):
-            raise ValueError(f"predictive: quantiles must be at most {MAX_QUANTILES} numbers in [0, 1], got {quantiles!r}")
+        qs = _quantiles(quantiles, "predictive")
         x, w, n, s1, s2 = self._rows_and_weights(x, w, "predictive")
         R, nq = self.n_predict, len(qs)
-        pin = self.predict_tile
-        tile, slab = predict_tiles(n, R, nq)
-        if pin:
-            tile, slab = (int(pin[0]), int(pin[1])) if isinstance(pin, (tuple, list)) else (int(pin), slab)
-        words = predict_scratch_words(n, R, nq)
-        if self._pscratch is None or self._pscratch.numel() < words or self._pscratch.device != x.device:
-            self._pscratch = torch.empty(words, dtype=torch.int64, device=x.device)      # kept: no allocation per call
+        tile, slab = self._predict_launch(n, R, nq)
+        scratch = self._kept_scratch("_pscratch", predict_scratch_words(n, R, nq), x.device)
         out = torch.empty((2 + nq, R), dtype=torch.float64, device=x.device)
         self._check(self.lib.tphu_predictive(self._stream(x), x.data_ptr(), w.data_ptr(), n, R, qs.ctypes.data, nq, out.data_ptr(),
-                                             self._pscratch.data_ptr(), self._pscratch.numel(), tile, slab, *self._data()),
-                    "tphu_predictive")
+                                             scratch.data_ptr(), scratch.numel(), tile, slab, *self._data()), "tphu_predictive")
         res = out.cpu().numpy()
         return {"mean": res[0].copy(), "var": res[1].copy(), "quantiles": res[2:].copy(), "n_rows": n, "ess": s1 * s1 / s2}
 
@@ -809,28 +817,21 @@ class HipCallbacks:
         import torch
         if not self.n_replicate:
             raise TempestHipError("HipCallbacks.replicated: the source defines no replicate(...) (give it and n_replicate=)")
-        qs = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
-        if qs.ndim != 1 or len(qs) > MAX_QUANTILES or not np.all((qs >= 0.0) & (qs <= 1.0)):
-            raise ValueError(f"replicated: quantiles must be at most {MAX_QUANTILES} numbers in [0, 1], got {quantiles!r}")
+        qs = _quantiles(quantiles, "replicated")
         if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
             raise ValueError(f"replicated: seed must be an int in [0, 2^64), got {seed!r}")
         x, w, n, s1, s2 = self._rows_and_weights(x, w, "replicated")
         if n >= 2 ** 32:
             raise ValueError(f"replicated: at most 2^32 - 1 rows (the row index is a 32-bit counter word of the noise), got {n}")
         R, nq = self.n_replicate, len(qs)
-        pin = self.predict_tile
-        tile, slab = predict_tiles(n, R, nq)
-        if pin:
-            tile, slab = (int(pin[0]), int(pin[1])) if isinstance(pin, (tuple, list)) else (int(pin), slab)
-        words = replicate_scratch_words(n, R, nq)
-        if self._yscratch is None or self._yscratch.numel() < words or self._yscratch.device != x.device:
-            self._yscratch = torch.empty(words, dtype=torch.int64, device=x.device)      # kept: no allocation per call
+        tile, slab = self._predict_launch(n, R, nq)
+        scratch = self._kept_scratch("_yscratch", replicate_scratch_words(n, R, nq), x.device)
         out = torch.empty((3 + nq) * R + 3, dtype=torch.float64, device=x.device)
         data = self._data()
         obs = self._dev_tables[self.observed].data_ptr() if self.observed is not None else None
         self._check(self.lib.tphu_replicated(self._stream(x), x.data_ptr(), w.data_ptr(), n, R, qs.ctypes.data, nq, int(seed), obs,
-                                             1 if self.has_discrepancy else 0, out.data_ptr(), self._yscratch.data_ptr(),
-                                             self._yscratch.numel(), tile, slab, *data), "tphu_replicated")
+                                             1 if self.has_discrepancy else 0, out.data_ptr(), scratch.data_ptr(), scratch.numel(),
+                                             tile, slab, *data), "tphu_replicated")
         flat = out.cpu().numpy()
         res = flat[:(3 + nq) * R].reshape(3 + nq, R)
         ret = {"mean": res[0].copy(), "var": res[1].copy(), "quantiles": res[2:2 + nq].copy(), "n_rows": n, "ess": s1 * s1 / s2,
@@ -860,10 +861,9 @@ class HipCallbacks:
         R = self.n_terms
         tile = int(self.pointwise_tile) or pointwise_tiles(n, R)
         words = pointwise_scratch_words(n, R)
-        if self._wscratch is None or self._wscratch.numel() < words or self._wscratch.device != x.device:
-            self._wscratch = torch.empty(words, dtype=torch.int64, device=x.device)      # kept: no allocation per call
+        scratch = self._kept_scratch("_wscratch", words, x.device)
         out = torch.empty((len(POINTWISE_KEYS), R), dtype=torch.float64, device=x.device)
-        self._check(self.lib.tphu_pointwise(self._stream(x), x.data_ptr(), w.data_ptr(), n, R, out.data_ptr(), self._wscratch.data_ptr(),
+        self._check(self.lib.tphu_pointwise(self._stream(x), x.data_ptr(), w.data_ptr(), n, R, out.data_ptr(), scratch.data_ptr(),
                                             words, tile, *self._data()), "tphu_pointwise")
         res = {k: v.copy() for k, v in zip(POINTWISE_KEYS, out.cpu().numpy())}
 
@@ -895,7 +895,6 @@ class HipCallbacks:
         self._check(self.lib.tphu_accept(self._stream(u), int(kernel_id), float(beta), p(u), p(x), p(logl), p(uprime),
                                          p(maha_u), p(maha_up), p(assign), n, n, int(K), p(dof), int(seed), int(tick),
                                          int(item0), p(sums), p(ctl), p(partials), p(pending), *self._data()), "tphu_accept")
-
 
     def can_fuse_step(self, K, has_assign, n) -> bool:
         """The whole step (proposal + callbacks + Metropolis update) in ONE kernel: register proposal kernel only

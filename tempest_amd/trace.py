@@ -1310,25 +1310,27 @@ def emit_source(graphs, tables=None):
     (kind, k); discrepancy uses its `y` directly."""
     D = "" if tables is None else ", const tphu_data& D"
     parts = ["// emitted by tempest_amd.trace_callbacks (DESIGN.md section 11): values live in registers, one statement per graph node"]
-    parts.append(emit(graphs["prior_transform"], f"__device__ void prior_transform(const double* u, double* x{D})", "u",
-                      lambda k, t: f"x[{k}] = {t};"))
-    if "log_likelihood_term" in graphs:
-        parts.append(emit(graphs["log_likelihood_term"], f"__device__ double log_likelihood_term(const double* x, int64_t r{D})", "x",
-                          lambda k, t: f"return {t};"))
-    else:
-        parts.append(emit(graphs["log_likelihood"], f"__device__ double log_likelihood(const double* x{D})", "x", lambda k, t: f"return {t};"))
-    if "predict" in graphs:
-        parts.append(emit(graphs["predict"], f"__device__ double predict(const double* x, int64_t r{D})", "x", lambda k, t: f"return {t};"))
-    if "derived" in graphs:
-        parts.append(emit(graphs["derived"], f"__device__ void derived(const double* x, double* out{D})", "x",
-                          lambda k, t: f"out[{k}] = {t};"))
-    if "replicate" in graphs:
-        parts.append(emit(graphs["replicate"], f"__device__ double replicate(const double* x, int64_t r, const tphu_noise& g{D})", "x",
-                          lambda k, t: f"return {t};"))
-    if "discrepancy" in graphs:
-        parts.append(emit(graphs["discrepancy"], f"__device__ double discrepancy(const double* x, int64_t r, double y{D})", "x",
-                          lambda k, t: f"return {t};"))
+    names = ["prior_transform", "log_likelihood_term" if "log_likelihood_term" in graphs else "log_likelihood"]
+    for name in names + [n for n in ("predict", "derived", "replicate", "discrepancy") if n in graphs]:
+        signature, arg, store = _EMITTED[name]
+        parts.append(emit(graphs[name], f"__device__ {signature}{D})", arg, store))
     return "\n".join(parts) + "\n"
+
+
+def _returned(k, t):
+    return f"return {t};"
+
+
+# graph name -> (signature up to the data argument, input name, the statement that stores output k)
+_EMITTED = {
+    "prior_transform": ("void prior_transform(const double* u, double* x", "u", lambda k, t: f"x[{k}] = {t};"),
+    "log_likelihood_term": ("double log_likelihood_term(const double* x, int64_t r", "x", _returned),
+    "log_likelihood": ("double log_likelihood(const double* x", "x", _returned),
+    "predict": ("double predict(const double* x, int64_t r", "x", _returned),
+    "derived": ("void derived(const double* x, double* out", "x", lambda k, t: f"out[{k}] = {t};"),
+    "replicate": ("double replicate(const double* x, int64_t r, const tphu_noise& g", "x", _returned),
+    "discrepancy": ("double discrepancy(const double* x, int64_t r, double y", "x", _returned),
+}
 
 
 def probe_batch(n_dim, rows=PROBE_ROWS, seed=PROBE_SEED):
@@ -1384,6 +1386,20 @@ def layered_sum(terms, chunk, block):
     return _seq_sum_last(t)
 
 
+def _eager(report, name, dev, run):
+    """run(dev), the eager side of the probe where the compiled code runs; run("cpu") without a device (dev None) or where the
+    function's constants were captured on the host, and that alone.  report["eager_on"][name] says which."""
+    if dev is not None:
+        try:
+            report["eager_on"][name] = "device"
+            return run(dev)
+        except RuntimeError as e:
+            if "Expected all tensors to be on the same device" not in str(e):
+                raise
+    report["eager_on"][name] = "cpu"
+    return run("cpu")
+
+
 def _probe_replicate(cb, graphs, data, x, on_device, report, replicate, discrepancy, D_on, chunks):
     """The (name, eager, traced) pairs of replicate and discrepancy (see `probe`)."""
     import torch
@@ -1404,15 +1420,7 @@ def _probe_replicate(cb, graphs, data, x, on_device, report, replicate, discrepa
         return out
 
     def eager(xs, items):
-        if on_device:
-            try:
-                report["eager_on"]["replicate"] = "device"
-                return eager_on(cb.device or "cuda", xs, items)
-            except RuntimeError as e:
-                if "Expected all tensors to be on the same device" not in str(e):
-                    raise
-        report["eager_on"]["replicate"] = "cpu"
-        return eager_on("cpu", xs, items)
+        return _eager(report, "replicate", (cb.device or "cuda") if on_device else None, lambda dev: eager_on(dev, xs, items))
 
     ey, et, ty, tt = [], [], [], []
     if on_device:                                    # at most 8 rows, each alone with weight 1: item 0, mean = replicate exactly
@@ -1474,17 +1482,10 @@ def probe(cb, prior_transform, log_likelihood, derived=None, predict=None, repli
         return tensors[dev]
 
     def eager(name, fn, a, with_data=False):
-        t = torch.from_numpy(a)
-        if on_device:
-            try:
-                report["eager_on"][name] = "device"
-                dev = cb.device or "cuda"
-                return fn(t.to(dev), *((D_on(dev),) if with_data else ())).detach().cpu().numpy()
-            except RuntimeError as e:   # constants captured on the host, and that alone: the eager side is evaluated there
-                if "Expected all tensors to be on the same device" not in str(e):
-                    raise
-        report["eager_on"][name] = "cpu"
-        return torch.as_tensor(fn(t, *((D_on("cpu"),) if with_data else ()))).detach().cpu().numpy()
+        def run(dev):
+            y = fn(torch.from_numpy(a).to(dev), *((D_on(dev),) if with_data else ()))
+            return (torch.as_tensor(y) if dev == "cpu" else y).detach().cpu().numpy()
+        return _eager(report, name, (cb.device or "cuda") if on_device else None, run)
 
     def traced(name, a):
         if on_device:
@@ -1542,18 +1543,10 @@ def probe(cb, prior_transform, log_likelihood, derived=None, predict=None, repli
 
 def _extent(v, what, host):
     """n_terms / n_predict: the name of a data entry (its length, or its rows), or an int that some entry has as that extent."""
+    from .hipcallbacks import _extent as extent
     if host is None:
         raise ValueError(f"trace_callbacks: {what}= goes with data= (the term and predict functions read the observations from D)")
-    if isinstance(v, str):
-        if v not in host:
-            raise ValueError(f"trace_callbacks: {what}={v!r} names no data entry")
-        return int(host[v].shape[0])
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) <= 0:
-        raise ValueError(f"trace_callbacks: {what} must be a positive int or the name of a data entry, got {v!r}")
-    if not any(a.shape[0] == int(v) for a in host.values()):
-        raise ValueError(f"trace_callbacks: {what}={int(v)} is the length (or the number of rows) of no data entry: the traced function "
-                         "has nothing to read per term")
-    return int(v)
+    return extent(v, what, host, "trace_callbacks", of_an_entry=True)
 
 
 def _is_f64(a):

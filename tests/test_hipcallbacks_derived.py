@@ -231,8 +231,8 @@ def test_derived_validation_raises_before_the_compiler_runs(source, kw, match, m
 def test_the_word_derived_in_a_comment_is_not_a_definition(monkeypatch):
     import tempest_amd as tp
     from tempest_amd import hipcallbacks
-    assert not hipcallbacks._has_derived(BASE + "// the rate is derived (see eq. 3) from x\n")
-    assert hipcallbacks._has_derived(BASE + ARITH)
+    assert not hipcallbacks._defines(BASE + "// the rate is derived (see eq. 3) from x\n", "derived")
+    assert hipcallbacks._defines(BASE + ARITH, "derived")
     monkeypatch.setattr(hipcallbacks, "build_plugin", lambda *a, **k: pytest.fail("the compiler ran"))
     with pytest.raises(ValueError, match="goes with a source that defines"):
         tp.HipCallbacks(BASE + "// derived (see eq. 3)\n", 4, n_derived=1)

@@ -313,9 +313,9 @@ def test_predict_validation_raises_before_the_compiler_runs(source, kw, match, m
 
 def test_the_word_predict_in_a_comment_is_not_a_definition():
     from tempest_amd import hipcallbacks
-    assert not hipcallbacks._has_predict(BASE + "// the band we predict (see eq. 3)\n")
-    assert not hipcallbacks._has_predict(BASE + "// double predictions(\n")
-    assert hipcallbacks._has_predict(BASE + PRED_X) and hipcallbacks._has_predict(WHOLE_D + PRED_D)
+    assert not hipcallbacks._defines(BASE + "// the band we predict (see eq. 3)\n", "predict")
+    assert not hipcallbacks._defines(BASE + "// double predictions(\n", "predict")
+    assert hipcallbacks._defines(BASE + PRED_X, "predict") and hipcallbacks._defines(WHOLE_D + PRED_D, "predict")
 
 
 def test_tile_rule_and_scratch():

@@ -263,8 +263,9 @@ def test_replicate_validation_raises_before_the_compiler_runs(source, kw, match,
 
 def test_the_words_in_a_comment_are_no_definitions():
     from tempest_amd import hipcallbacks as H
-    assert not H._has_replicate(BASE + "// we replicate( the data\n") and not H._has_replicate(BASE + "// double replicated(\n")
-    assert H._has_replicate(BERN) and H._has_discrepancy(BERN) and H._has_replicate(REP_X) and not H._has_discrepancy(GAUSS_PRIOR + GAUSS_REP)
+    assert not H._defines(BASE + "// we replicate( the data\n", "replicate") and not H._defines(BASE + "// double replicated(\n", "replicate")
+    assert H._defines(BERN, "replicate") and H._defines(BERN, "discrepancy") and H._defines(REP_X, "replicate")
+    assert not H._defines(GAUSS_PRIOR + GAUSS_REP, "discrepancy")
 
 
 def test_plugin_text_and_key_carry_replicate_only_with_it():

@@ -4,7 +4,7 @@ __version__ = "0.1.0"
 
 from .sampler import Sampler
 
-__all__ = ["Sampler", "HipCallbacks", "trace_callbacks", "Noise"]
+__all__ = ["Sampler", "HipCallbacks", "trace_callbacks", "Noise", "Prior", "priors"]
 
 
 def __getattr__(name):          # lazy: importing the package must not need hipcc or a GPU
@@ -17,4 +17,10 @@ def __getattr__(name):          # lazy: importing the package must not need hipc
     if name == "Noise":         # the host twin of a plugin's tphu_noise: the g of trace_callbacks(replicate=) in eager use
         from .trace import Noise
         return Noise
+    if name == "Prior":         # independent priors column by column: a traceable prior_transform, its HIP text, its log density
+        from .priors import Prior
+        return Prior
+    if name == "priors":
+        import importlib
+        return importlib.import_module(".priors", __name__)
     raise AttributeError(name)

@@ -16,6 +16,10 @@ compute the textbook form, the graph records what that kernel computes: `x / c` 
 sum * (1 / k), `x ** 2` is x * x.  Everything outside the supported list is refused with a TraceError that
 names the operation, the user's source line and what to write instead.
 
+torch.special.ndtri and torch.erfinv are the exception to "what the eager kernel computes": they are emitted as calls of
+csrc/quantile.h (Wichura's AS241, its text pasted in front of the source), and `ndtri_host` / `erfinv_host` below restate that
+header operation by operation -- the replay of these two nodes is their specification, a few ulp from eager torch's other algorithm.
+
 Likelihoods over observed data (`data=`, `n_terms=`, `predict=`): the callbacks take the entries as a second argument D; the term
 function (x, D) -> (n, n_terms) returns one column per observation and is emitted as `log_likelihood_term(x, r, D)`, the column at
 the term index r -- the library owns the sum.  Under the tracer an entry has no particle axis: one as long as the term axis is a
@@ -31,6 +35,7 @@ import math
 import os
 import struct
 import sys
+from pathlib import Path
 
 import numpy as np
 
@@ -91,7 +96,9 @@ def _call(fn, *args):
 _BINARY = {"add": "+", "sub": "-", "mul": "*", "div": "/"}
 _CALL2 = {"pow": "pow", "max": "tphu_tr_max", "min": "tphu_tr_min"}
 _UNARY = {"abs": "fabs", "sqrt": "sqrt", "rsqrt": "rsqrt", "exp": "exp", "expm1": "expm1", "log": "log", "log1p": "log1p",
-          "sin": "sin", "cos": "cos", "tan": "tan", "tanh": "tanh", "atan": "atan", "erf": "erf", "erfc": "erfc", "lgamma": "lgamma"}
+          "sin": "sin", "cos": "cos", "tan": "tan", "tanh": "tanh", "atan": "atan", "erf": "erf", "erfc": "erfc", "lgamma": "lgamma",
+          "ndtri": "tphu_ndtri", "erfinv": "tphu_erfinv"}
+_QUANTILE = ("ndtri", "erfinv")                 # emitted as calls of csrc/quantile.h, whose text emit_source pastes in front
 _COMPARE = {"gt": ">", "lt": "<", "ge": ">=", "le": "<=", "eq": "==", "ne": "!="}
 _BOOL_OPS = set(_COMPARE) | {"and", "or", "not"}
 _NOISE = {"noise_normal": "normal", "noise_uniform": "uniform"}
@@ -225,13 +232,71 @@ def _host_array(v):
     return np.asarray(v.detach().cpu().numpy() if _is_tensor(v) else v, dtype=np.float64)
 
 
+def quantile_header():
+    """The text of csrc/quantile.h: the device functions behind the "ndtri" and "erfinv" nodes."""
+    return (Path(__file__).resolve().parent / "csrc" / "quantile.h").read_text()
+
+
+# csrc/quantile.h restated: Wichura's AS241 (PPND16), the coefficients in the order of the header's argument lists (c0 first)
+_AS241 = {
+    "A": (3.3871328727963666080, 133.14166789178437745, 1971.5909503065514427, 13731.693765509461125, 45921.953931549871457,
+          67265.770927008700853, 33430.575583588128105, 2509.0809287301226727),
+    "B": (1.0, 42.313330701600911252, 687.18700749205790830, 5394.1960214247511077, 21213.794301586595867, 39307.895800092710610,
+          28729.085735721942674, 5226.4952788528545610),
+    "C": (1.42343711074968357734, 4.63033784615654529590, 5.76949722146069140550, 3.64784832476320460504, 1.27045825245236838258,
+          0.241780725177450611770, 0.0227238449892691845833, 7.74545014278341407640e-4),
+    "D": (1.0, 2.05319162663775882187, 1.67638483018380384940, 0.689767334985100004550, 0.148103976427480074590,
+          0.0151986665636164571966, 5.47593808499534494600e-4, 1.05075007164441684324e-9),
+    "E": (6.65790464350110377720, 5.46378491116411436990, 1.78482653991729133580, 0.296560571828504891230, 0.0265321895265761230930,
+          0.00124266094738807843860, 2.71155556874348757815e-5, 2.01033439929228813265e-7),
+    "F": (1.0, 0.599832206555887937690, 0.136929880922735805310, 0.0148753612908506148525, 7.86869131145613259100e-4,
+          1.84631831751005468180e-5, 1.42151175831644588870e-7, 2.04426310338993978564e-15),
+}
+
+
+def _poly(r, c):
+    s = np.full_like(r, c[7])
+    for k in range(6, -1, -1):
+        s = s * r + c[k]
+    return s
+
+
+def _ndtri_core(q, t):
+    """tphu_ndtri_core of csrc/quantile.h in NumPy float64: the same operations in the same order, every region evaluated for every
+    element and the element's own one kept (an element's value does not depend on the others).  log comes from torch on the CPU."""
+    with np.errstate(all="ignore"):
+        r = 0.180625 - q * q
+        central = q * _poly(r, _AS241["A"]) / _poly(r, _AS241["B"])
+        r = np.sqrt(-_torch_unary("log")(t))
+        near = _poly(r - 1.6, _AS241["C"]) / _poly(r - 1.6, _AS241["D"])
+        far = _poly(r - 5.0, _AS241["E"]) / _poly(r - 5.0, _AS241["F"])
+        x = np.where(r <= 5.0, near, far)
+        x = np.where(t > 0.0, x, np.inf)
+        return np.where(np.abs(q) <= 0.425, central, np.where(q < 0.0, -x, x))
+
+
+def ndtri_host(p):
+    """tphu_ndtri of csrc/quantile.h in NumPy: what the device computes for torch.special.ndtri under the tracer."""
+    p = np.ascontiguousarray(p, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        return np.where((p >= 0.0) & (p <= 1.0), _ndtri_core(p - 0.5, np.fmin(p, 1.0 - p)), np.nan)
+
+
+def erfinv_host(y):
+    """tphu_erfinv of csrc/quantile.h in NumPy: what the device computes for torch.erfinv under the tracer."""
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        return np.where(np.abs(y) <= 1.0, _ndtri_core(0.5 * y, 0.5 * (1.0 - np.abs(y))) * 0.70710678118654752440, np.nan)
+
+
 def replay(graph, array, data=None, noise=None, y=None):
     """The graph evaluated in NumPy float64, node by node in emission order, on the (n, n_in) rows of `array`: what the emitted
     device function computes -- (n,) + graph.out_shape; (n, T) for a term, predict, replicate or discrepancy graph, whose nodes are
     evaluated for every (row, term index) -- the device function is called once per pair.  data: {name: array} for graphs that read
     data entries; noise: a `Noise` over the n rows (anything with .normal(k) / .uniform(k) -> (n, T)) for a replicate graph that
     draws; y: (T,) -- one row for all -- or (n, T), the y of a discrepancy graph.
-    exp, log and the other transcendentals, erf, erfc and lgamma come from torch on the CPU."""
+    exp, log and the other transcendentals, erf, erfc and lgamma come from torch on the CPU; ndtri and erfinv are `ndtri_host` /
+    `erfinv_host`, the restatement of csrc/quantile.h -- NOT eager torch's, which computes them with another algorithm."""
     a = np.ascontiguousarray(array, dtype=np.float64)
     if a.ndim != 2 or a.shape[1] != graph.n_in:
         raise ValueError(f"replay: expected (n, {graph.n_in}) rows, got {a.shape}")
@@ -286,6 +351,8 @@ def replay(graph, array, data=None, noise=None, y=None):
                 val[i] = un[op](val[args[0]])
             elif op in ("erf", "erfc", "lgamma"):
                 val[i] = _torch_unary(op)(val[args[0]])
+            elif op in _QUANTILE:
+                val[i] = (ndtri_host if op == "ndtri" else erfinv_host)(val[args[0]])
             elif op == "where":
                 val[i] = np.where(val[args[0]], val[args[1]], val[args[2]])
             else:                                    # pragma: no cover
@@ -970,9 +1037,40 @@ _TORCH = {
     "__rmatmul__": lambda a, b: _matmul(b, a), "cumsum": _cumsum,
 }
 for _n in _UNARY:
-    if _n != "abs":
+    if _n != "abs" and _n not in _QUANTILE:
         _TORCH[_n] = (lambda op: lambda a: _unary(op, a))(_n)
 _TORCH["arctan"] = _TORCH["atan"]
+
+
+def _quantile(op):
+    def handler(a, out=None):
+        if out is not None:
+            _refuse(f"torch.{op}(..., out=)", "only true elementwise results are traced", f"torch.special.{op}(x)")
+        f = sys._getframe(1)
+        while f is not None:                         # Normal(...).icdf(u) arrives here as torch.erfinv(2 u - 1)
+            if (os.sep + "torch" + os.sep + "distributions" + os.sep) in f.f_code.co_filename:
+                _refuse("a torch.distributions object (icdf)", "its methods check and convert their argument as eager tensors, and "
+                        "what they compute differs from one torch version to the next", "tempest_amd.Prior([tempest_amd.priors.Normal("
+                        "mu, s), ...]).transform, or the transform written out: mu + s * torch.special.ndtri(u)")
+            f = f.f_back
+        return _unary(op, a)
+    return handler
+
+
+def _not_traced(name, instead):
+    def handler(*a, **k):
+        _refuse(name, "it is outside the supported operation list: of the normal distribution's functions the tracer has erf, erfc, "
+                "torch.special.ndtri and torch.erfinv", instead)
+    return handler
+
+
+for _n in _QUANTILE:
+    _TORCH[_n] = _TORCH["special_" + _n] = _quantile(_n)
+_REFUSED = {"ndtr": "0.5 * torch.erfc(-x * 0.7071067811865476)",
+            "log_ndtr": "torch.log(0.5 * torch.erfc(-x * 0.7071067811865476)) (it loses the far lower tail: keep x above -37)",
+            "erfcinv": "-torch.special.ndtri(0.5 * y) * 0.7071067811865476"}
+for _n, _instead in _REFUSED.items():
+    _TORCH[_n] = _TORCH["special_" + _n] = _not_traced(f"torch.special.{_n}", _instead)
 for _n, _alts in (("add", ("__add__", "__radd__")), ("mul", ("multiply", "__mul__", "__rmul__")), ("sub", ("subtract", "__sub__")),
                   ("div", ("divide", "true_divide", "__truediv__"))):
     for _a in (_n,) + _alts:
@@ -1008,6 +1106,8 @@ for _n in ("neg", "negative", "abs", "absolute", "square", "reciprocal", "sigmoi
 for _n in ("add", "mul", "sub", "truediv", "rsub", "rtruediv", "gt", "lt", "ge", "le", "eq", "ne", "and", "or"):
     setattr(TV, f"__{_n}__", _method(f"__{_n}__"))
 TV.cumsum = _method("cumsum")
+for _n in _REFUSED:
+    setattr(TV, _n, _method(_n))
 TV.__radd__ = lambda self, o: _binary("add", o, self)
 TV.__rmul__ = lambda self, o: _binary("mul", o, self)
 TV.__rand__ = lambda self, o: _logical("and", o, self)
@@ -1310,6 +1410,8 @@ def emit_source(graphs, tables=None):
     (kind, k); discrepancy uses its `y` directly."""
     D = "" if tables is None else ", const tphu_data& D"
     parts = ["// emitted by tempest_amd.trace_callbacks (DESIGN.md section 11): values live in registers, one statement per graph node"]
+    if any(g.nodes[i][0] in _QUANTILE for g in graphs.values() for i in g.live()):
+        parts.insert(0, quantile_header().rstrip("\n"))          # pasted, not #included: build_plugin hashes the text
     names = ["prior_transform", "log_likelihood_term" if "log_likelihood_term" in graphs else "log_likelihood"]
     for name in names + [n for n in ("predict", "derived", "replicate", "discrepancy") if n in graphs]:
         signature, arg, store = _EMITTED[name]

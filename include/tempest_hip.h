@@ -107,8 +107,8 @@ int tph_warmup(tph_ctx* ctx);
 /* TPH_OPT_STAGED_REDRAW: 1 = 16 < n_dim <= 100, one mode, steps that are mostly REDRAWS (mcmc.py:239-249: early iterations of a
  * high-dimensional run): the row-walker kernel (propose_sm.hip: a lane per attempt with its normals in its column of a tile,
  * attempts advance four rows at a time and stop at their first out-of-bounds coordinate, several attempts of a particle in
- * flight, the first in-bounds one in attempt order wins).  0 = those steps through the multi-lane kernel.  The host (mcmc.py:
- * StepEngine) switches on the redraw probe, like TPH_OPT_BLOCKED.  TPH_OPT_SM_LANES: log2 of the lanes per particle (0 = by
+ * flight, the first in-bounds one in attempt order wins).  0 = those steps through the multi-lane kernel.  The host (regime.py:
+ * Regime.next, applied by StepEngine) switches on the redraw probe, like TPH_OPT_BLOCKED.  TPH_OPT_SM_LANES: log2 of the lanes per particle (0 = by
  * size); TPH_OPT_SM_THRESHOLD: rows of an attempt's normals kept in LDS, rounded up to 16 (0 = 32; the rows beyond live in
  * global scratch -- fewer rows, more waves per CU). */
 #define TPH_OPT_STAGED_REDRAW 9

@@ -11,6 +11,8 @@ from typing import Callable, Optional
 
 import numpy as np
 
+from .regime import REGIME_THRESHOLDS, Regime, RegimeOptions, regime_band  # noqa: F401  (the d > 16 proposal rule: regime.py)
+
 
 class PhiloxStream:
     """Host side of the counter-based RNG: a 64-bit seed and the tick handed to each RNG-consuming launch."""
@@ -59,59 +61,6 @@ def check_bounds(u, periodic=None, reflective=None):
     return bool(inside.all()) if u.ndim == 1 else inside.all(axis=-1)
 
 
-class RegimeOptions:
-    """Debugging switches of the d > 16 proposal regime (TEMPEST_AMD_STAGED / _SCREEN / _BLK_MFMA / _BLK_FAN / _SM_LANES): read from
-    the environment ONCE, when an engine is built -- never in the step path."""
-    __slots__ = ("walker_ok", "screen", "blk_mfma", "fan", "sm_lanes", "pin")
-
-    def __init__(self, walker_ok=True, screen=True, blk_mfma=True, fan=1, sm_lanes=0, pin=""):
-        self.walker_ok, self.screen, self.blk_mfma, self.fan, self.sm_lanes = walker_ok, screen, blk_mfma, int(fan), int(sm_lanes)
-        # TEMPEST_AMD_REGIME=screened: every d > 16 step of a one-mode run through the screened batches, whatever the probe says.
-        # Their proposals are the FP64 row walker's bit for bit and a particle's arithmetic never depends on its neighbours, so a
-        # run pinned there is bitwise the same on any number of GPUs (the adaptive rule sends a step to the matrix-core rounds by
-        # the RANK's own list lengths, and those kernels agree with the batches to rounding only)
-        self.pin = pin
-
-    @classmethod
-    def from_env(cls, env=None):
-        import os
-        env = os.environ if env is None else env
-        return cls(walker_ok=env.get("TEMPEST_AMD_STAGED", "1") != "0", screen=env.get("TEMPEST_AMD_SCREEN", "1") != "0",
-                   blk_mfma=env.get("TEMPEST_AMD_BLK_MFMA", "1") != "0", fan=int(env.get("TEMPEST_AMD_BLK_FAN", "1")),
-                   sm_lanes=int(env.get("TEMPEST_AMD_SM_LANES", "0")), pin=env.get("TEMPEST_AMD_REGIME", ""))
-
-
-# Crossovers of the redraw probe (mean attempts per particle of a step) between the d > 16 proposal kernels.  One row per
-# dimension band (the first whose n_dim_min <= n_dim):  (n_dim_min, up, down, cap, floor) --
-#   up:    the blocked rounds are left when THEIR probe, the geometric estimate n / (n - first-attempt failures), reaches it;
-#   down:  they are taken up again when the TRUE mean reported by the screened batches / the row walker falls below it
-#          (the hard particles near a wall pull the true mean above the estimate: hence two numbers, DESIGN 3i);
-#   cap, floor: at most `cap` rounds, and only while the expected failure list still holds `floor` particles.
-# All fitted on one MI355X with tools/regime_sweep.py; `source` names the sweep a row came from.
-REGIME_THRESHOLDS = {
-    "screened": {"source": "profiles/r04_regime_sweep.jsonl, profiles/r04_regime_sweep_fan.jsonl (fanned-out list rounds); the crossover "
-                           "re-measured with the LDS-staged rounds of round 5: profiles/r05_regime_sweep.jsonl (unchanged)",
-                 "bands": ((64, 3.0, 5.0, 6, 64.0), (33, 3.4, 5.5, 8, 64.0), (17, 8.0, 13.0, 12, 64.0))},
-    "walker": {"source": "profiles/r03_propose_d50_d100.json (screen off: FP64 row walker, multi-lane straggler pass)",
-               "bands": ((64, 4.5, 8.0, 24, 24576.0), (17, 3.5, 5.0, 24, 24576.0))},
-    # several modes (matrix-core rounds over mode-pure tiles <-> per-mode screened batches / multi-lane kernel): leave at, return below
-    "several_modes": {"source": "profiles/r04_regime_sweep_fan.jsonl", "up": 13.0, "down": 8.0},
-    # multi-lane kernel: matrices from global memory (a quarter of the LDS) above, LDS-staged below
-    "unstaged": {"source": "profiles/r02_propose_d50_d100.json", "up": 8.0, "down": 4.0},
-    # a kernel switch retires the captured graph of the step: from the third switch in a row that comes within `recent` readings of
-    # the one before, the next has to wait (4, 8, ... 64 probe readings) -- a probe that sits on a threshold and flips every step
-    # costs a bounded number of captures (test_regime_rule_does_not_oscillate)
-    "dwell": {"first": 4, "max": 64, "recent": 8},
-}
-
-
-def regime_band(table, n_dim):
-    for row in REGIME_THRESHOLDS[table]["bands"]:
-        if n_dim >= row[0]:
-            return row[1:]
-    return REGIME_THRESHOLDS[table]["bands"][-1][1:]
-
-
 class StepEngine:
     """One MCMC step -- proposal, the two user callbacks, Metropolis update, sigma adaptation -- as a replayable
     hipGraph over persistent device buffers.
@@ -130,11 +79,17 @@ class StepEngine:
 
     SLOTS = 64          # mailbox ring: the host never runs more than a few steps ahead of the record it waits for
     _epoch = 0          # version counter of the mode statistics handed to the library (TPH_OPT_MODES_EPOCH)
+    blocked = property(lambda self: self.regime.blocked)        # the regime's parts, read by tests and tools
+    staged = property(lambda self: self.regime.staged)
+    unstaged = property(lambda self: self.regime.unstaged)
+    sm_lanes = property(lambda self: self.regime.sm_lanes)
 
     def __init__(self, ctx, kernel, n, K, has_assign, bc, log_likelihood, prior_transform, seed, item0, n_global,
                  n_steps, n_max, comm_active, use_graph=True, plugin=None):
+        import os
         import torch
         from types import SimpleNamespace
+        from .device import STEP_STATE_LEN, vshards_for
         self.plugin = plugin
         d = ctx.n_dim
         self.ctx, self.kernel, self.n, self.K, self.bc = ctx, kernel, n, K, bc
@@ -144,7 +99,6 @@ class StepEngine:
         # with the library's peer-to-peer exchange attached, the all-reduce of the step's sums is a kernel on the ctx stream:
         # it belongs to the step (and to its graph) like every other launch; otherwise the host calls the process group
         # (this rank's shard sums -- vl (1 + K) doubles, vl = its virtual shards of the canonical partition -- must fit one slot)
-        from .device import vshards_for
         world = max(1, int(round(n_global / n))) if n else 1
         vl = vshards_for(n * world) // world if (n * world) % 256 == 0 and vshards_for(n * world) % world == 0 else 1
         self.inline_reduce = bool(comm_active and ctx.p2p_active and 8 * vl * (1 + K) <= 32768)   # one exchange slot (p2p.h)
@@ -161,23 +115,12 @@ class StepEngine:
         # deferred Metropolis update: tph_accept records the decisions here, the NEXT tph_propose moves the accepted
         # proposals into place (its FP64 work hides the copy; in place it was a bandwidth-bound kernel of its own)
         self.pending = torch.zeros(n, dtype=torch.uint8, device=ctx.device)
-        from .device import STEP_STATE_LEN
         self.ctl = ctx.zeros(STEP_STATE_LEN)
         self.ctl_host = torch.zeros(STEP_STATE_LEN, dtype=torch.float64).pin_memory()
-        self.unstaged = False          # d > 16 proposal kernel without LDS-staged matrices (redraw-dominated steps)
-        self.blocked = 0               # d > 16: rounds of the blocked kernel (attempts in lockstep) before the straggler pass; 0 = off
-        self.staged, self.sm_lanes = False, 0      # d > 16: row-walker kernel for redraw-dominated steps, its lanes per particle (log2)
         self._opts = RegimeOptions.from_env()      # the regime's debugging switches, read here and nowhere in the step path
-        import os
+        self.regime = Regime.initial(d, K, has_assign, self._opts)      # the d > 16 proposal kernel of the next steps (regime.py)
         env = os.environ.get("TEMPEST_AMD_STEP_TIMEOUT")
         self._step_timeout = float(env) if env else None      # seconds a step's record may take (None: until the stream goes idle)
-        self._since, self._dwell, self._quick = 1 << 30, 0, 0      # readings since the last kernel switch; readings the next must wait; quick switches in a row
-        self._screened = self._opts.screen and d <= 112
-        if (d > 16 and self._screened and self._opts.walker_ok and ((K == 1 and not has_assign) or (1 < K <= 64 and has_assign))):
-            # Nothing is known about the redraw rate before an engine's first steps: they run as screened batches, whose time is
-            # flat in it (0.4-3 ms), instead of through the multi-lane kernel, whose time is not (30 ms per launch from the prior
-            # at 131 072 x 100-D: three such launches were 2 % of the config-5 shard's run); the probe of step 2 picks the regime.
-            self.staged = True
         # written by tph_adapt, polled here: the ring of step records and, behind it, the last record of a run made in ONE launch
         self._mail_all = torch.zeros(self.SLOTS + 1, 8, dtype=torch.float64).pin_memory()
         self.mailbox = self._mail_all[:self.SLOTS]
@@ -190,6 +133,8 @@ class StepEngine:
     def load(self, u, x, logl, assign, modes, beta, tick_base, sigma_init, counts):
         """Start a run: active set, proposal modes and the step-control block.  A graph needs fixed addresses, so
         the data is copied into the engine's persistent buffers; without one the caller's tensors are used as they are."""
+        import torch
+        from .device import OPT_MODES_EPOCH
         self.runs += 1
         if self.use_graph:
             if self._own is None:
@@ -200,23 +145,16 @@ class StepEngine:
                 self.assign.copy_(assign)
             m = self.modes
             m.means_dev.copy_(modes.means_dev.reshape(m.means_dev.shape)); m.chol_dev.copy_(modes.chol_dev.reshape(m.chol_dev.shape))
-            winv = getattr(modes, "winv_dev", None)
+            winv = modes.winv_dev if hasattr(modes, "winv_dev") else None
             if winv is None:            # mode statistics built outside ModeStatistics: L^-1 from the factors
                 winv = torch.linalg.inv(modes.chol_dev.reshape(m.chol_dev.shape))
             m.winv_dev.copy_(winv.reshape(m.winv_dev.shape)); m.dof_dev.copy_(modes.dof_dev.reshape(m.dof_dev.shape))
         else:
             self.u, self.logl, self.assign, self.modes = u, logl, assign, modes
         if self.ctx.n_dim > 16:        # new mode statistics: the library rebuilds its blocked copies of L and L^-1 once
-            from .device import OPT_BLOCKED, OPT_ML_UNSTAGED, OPT_MODES_EPOCH, OPT_SM_LANES, OPT_STAGED_REDRAW
             StepEngine._epoch += 1
             self.ctx.set_option(OPT_MODES_EPOCH, StepEngine._epoch)
-            # the proposal regime is an option of the ctx, which engines of other shapes share: re-assert this engine's
-            self.ctx.set_option(OPT_BLOCKED, int(self.blocked))
-            self.ctx.set_option(OPT_ML_UNSTAGED, 1 if self.unstaged else 0)
-            self.ctx.set_option(OPT_STAGED_REDRAW, 1 if self.staged else 0)
-            self.ctx.set_option(OPT_SM_LANES, self.sm_lanes)
-            from .device import OPT_SCREEN
-            self.ctx.set_option(OPT_SCREEN, 1 if self._screened else 0)
+            self._push_options()       # the proposal regime is an option of the ctx, which engines of other shapes share: re-assert this engine's
         self.sigmas.fill_(sigma_init)
         self.pending.zero_()
         self.counts.copy_(counts)
@@ -228,12 +166,12 @@ class StepEngine:
 
     def _enqueue(self):
         """The launches of one step on the current stream (ticks are offsets: the device adds base + 2 * steps done)."""
+        from .device import KERNEL_ID
         ctx = self.ctx
         if (self.plugin is not None and (not self.comm_active or self.inline_reduce)
                 and self.plugin.can_fuse_step(self.K, self.assign is not None, self.n)):
             # proposal, callbacks and Metropolis update in ONE kernel of the user's plugin (hipcallbacks.py); with ranks only
             # when tph_adapt exchanges the sums itself (otherwise the host needs them between two launches)
-            from .device import KERNEL_ID
             self.plugin.step(KERNEL_ID[self.kernel], self.u, self.logl, self.maha_u, self.modes, self.sigmas, self.bc,
                              self.seed, 1, 2, self.item0, self.ctl, self.partials)
             self._adapt(fold=True)
@@ -245,8 +183,7 @@ class StepEngine:
         # between the two launches (step(): tph_accept_sums_global)
         sums = None
         if self.plugin is not None and self.plugin.can_fuse_accept(self.n):   # callbacks compiled into the Metropolis kernel
-            from .device import KERNEL_ID                                      # (hipcallbacks.py; not where its sum over data is split)
-            xp = lp = None
+            xp = lp = None                                                     # (hipcallbacks.py; not where its sum over data is split)
             self.plugin.accept(KERNEL_ID[self.kernel], 0.0, self.u, None, self.logl, self.up, self.maha_u, self.maha_up,
                                self.assign, self.K, self.modes.dof_dev, self.seed, 2, self.item0, sums,
                                ctl=self.ctl, partials=self.partials, pending=self.pending)
@@ -273,6 +210,7 @@ class StepEngine:
         """Launch the run loaded by load() as ONE kernel and wait for its last step's record; None if the device refused the
         launch (nothing ran: step as usual)."""
         import torch
+        from ._lib import TempestHipError
         from .device import KERNEL_ID
         if self._run_bufs is None:
             tiles = (self.n + 255) // 256
@@ -285,158 +223,69 @@ class StepEngine:
                                1, 2, self.item0, self.ctl, partials2, barrier, self.counts, self.n_global, self.n_steps,
                                self.n_max, self._mail_all, self.SLOTS, self.n_max * d + 1):
             return None
-        self._poll(last, None, "the run")
+        self._poll(last, None)
         if last[1] < 0.0:
-            from ._lib import TempestHipError
             raise TempestHipError("MCMC run in one launch was abandoned on the device (a workgroup timed out at the grid barrier)")
         if last[1] == 0.0:
-            from ._lib import TempestHipError
             raise TempestHipError("MCMC run in one launch ended without its stopping rule having fired")
         return last[:6].copy()
 
-    def _poll(self, rec, step, what, timeout=None):
-        """Spin on a pinned record until its sequence field shows `step` (None: any step); errors as in wait_record."""
+    def _poll(self, rec, step, timeout=None, late=None):
+        """Spin on a pinned record until its sequence field shows `step` (None: the record of a run in one launch, any step).  The
+        wait ends with an error only when the stream has gone IDLE without delivering the record (like tph_reweight_eval's poll)
+        or, if a `timeout` in seconds is given (TEMPEST_AMD_STEP_TIMEOUT), after that long: a step may legitimately take minutes
+        (an expensive likelihood, a callback that compiles on first use, a shared GPU).  `late` is called at every look at the
+        clock once the wait has lasted two seconds."""
         import time
         import torch
         if timeout is None:
             timeout = self._step_timeout
-        arrived = (lambda: rec[7] >= 0.0) if step is None else (lambda: rec[7] == step)
         spins, t0 = 0, None
-        while not arrived():
+        while (not rec[7] >= 0.0 if step is None else rec[7] != step):
             spins += 1
             if spins & 0x3FFF == 0:
-                now = time.monotonic()
-                t0 = t0 or now
-                if now - t0 > 0.05:
-                    time.sleep(0)
-                if now - t0 > 2.0 and torch.cuda.current_stream(self.ctx.device).query() and not arrived():
-                    from ._lib import TempestHipError
-                    raise TempestHipError(f"{what}: the stream is idle and the device never delivered the record")
-                if timeout is not None and now - t0 > timeout:
-                    from ._lib import TempestHipError
-                    raise TempestHipError(f"{what}: no record from the device after {timeout} s")
-
-    def wait_record(self, step, timeout=None):
-        """State record (tph_adapt's state[0..5]) of step `step`, polled from the pinned mailbox.  The wait ends with an
-        error only when the stream has gone IDLE without delivering the record (like tph_reweight_eval's poll) or, if a
-        `timeout` in seconds is given (TEMPEST_AMD_STEP_TIMEOUT), after that long: a step may legitimately take minutes
-        (an expensive likelihood, a callback that compiles on first use, a shared GPU)."""
-        import time
-        import torch
-        if timeout is None:
-            timeout = self._step_timeout
-        rec = self.mailbox_np[step % self.SLOTS]
-        spins, t0 = 0, None
-        while rec[7] != step:
-            spins += 1
-            if spins & 0x3FFF == 0:
+                # (everything an error needs is fetched here, off the path of a record that is already there: the step loop with
+                # torch callbacks shows a microsecond of host work per step, profiles/regime_refactor_ab.json)
+                from ._lib import TempestHipError
+                what, record = ("the run", "the record") if step is None else (f"MCMC step {step}", "the step's record")
                 now = time.monotonic()
                 t0 = t0 or now
                 if now - t0 > 0.05:
                     time.sleep(0)                 # long wait: let other Python threads run between polls
-                if now - t0 > 2.0:
-                    self.ctx.p2p_status()         # raises if a peer never arrived at an exchange
-                if now - t0 > 2.0 and torch.cuda.current_stream(self.ctx.device).query() and rec[7] != step:
-                    from ._lib import TempestHipError
-                    raise TempestHipError(f"MCMC step {step}: the stream is idle and the device never delivered the step's record")
+                if now - t0 > 2.0 and late is not None:
+                    late()
+                if (now - t0 > 2.0 and torch.cuda.current_stream(self.ctx.device).query()
+                        and (not rec[7] >= 0.0 if step is None else rec[7] != step)):
+                    raise TempestHipError(f"{what}: the stream is idle and the device never delivered {record}")
                 if timeout is not None and now - t0 > timeout:
-                    from ._lib import TempestHipError
-                    raise TempestHipError(f"MCMC step {step}: no record from the device after {timeout} s")
+                    raise TempestHipError(f"{what}: no record from the device after {timeout} s")
+
+    def wait_record(self, step, timeout=None):
+        """State record (tph_adapt's state[0..5]) of step `step`, polled from the pinned mailbox; its redraw probe goes to the
+        regime rule."""
+        rec = self.mailbox_np[step % self.SLOTS]
+        self._poll(rec, step, timeout, late=self.ctx.p2p_status)      # (raises if a peer never arrived at an exchange)
         self._regime(rec[6])
         return rec[:6].copy()
 
+    def _push_options(self):
+        """The engine's regime as options of the ctx: the one place that sets them."""
+        from . import device
+        for name, value in self.regime.options(self.ctx.n_dim, self._opts):
+            self.ctx.set_option(getattr(device, name), value)
+
     def _regime(self, mean_attempts):
-        """The d > 16 proposal kernels report the mean number of attempts per particle of the step, and the host picks the
-        kernel for the next steps from it (thresholds: REGIME_THRESHOLDS above).  A captured graph has its kernels baked in: when
-        the rule asks for a different KERNEL than the graph holds (blocked <-> screened batches / walker <-> multi-lane; not for a
-        different number of rounds), the graph is retired and the step is captured again at its next launch -- an engine captured in
-        a run's redraw-dominated first iterations would otherwise walk rows for the rest of the run.  One mode:
-          * a step is a few attempts per particle: the blocked rounds (propose_blkm.hip: attempts in lockstep, 16 particles per
-            wave, both triangular products on the FP64 matrix cores) -- attempt 0 of everybody, further rounds over the particles
-            still out of bounds (fanned out), the rest finished by a screened launch over the list.  Its probe is the geometric
-            estimate n / (n - first-attempt failures);
-          * most attempts are redraws: the screened batches (propose_mf.hip; screen off: the FP64 row walker, propose_sm.hip).
-            Their probe is the true mean, which the hard particles near a wall pull above the geometric estimate (131 072 x
-            100-D: estimate 2.8 / true 4.7; 65 536 x 50-D: 2.1 / 2.7, 4.2 / 7.2) -- hence the two thresholds per band.
-        Several modes (K > 1, up to 64): the matrix-core rounds over mode-pure tiles while a step is a few attempts per particle,
-        their stragglers and the redraw-dominated steps through the per-mode screened batches (screen off: the multi-lane kernel,
-        un-staged while redraws dominate, LDS-staged once a step is about one attempt).
-        A switch back within a few readings of the last one makes the NEXT switch wait (REGIME_THRESHOLDS["dwell"]): a probe that
-        sits on a threshold and flips every step costs a bounded number of captures, not one per step."""
-        if self.ctx.n_dim <= 16 or not mean_attempts > 0.0:
+        """One reading of the redraw probe: the rule decides (Regime.next), the engine applies -- the regime's options into the
+        ctx, and a captured graph, which has its kernels baked in, retired when the rule asks for another KERNEL than it holds
+        (the step is captured again at its next launch)."""
+        old = self.regime
+        new = self.regime = old.next(mean_attempts, n_dim=self.ctx.n_dim, n=self.n, K=self.K, opts=self._opts,
+                                     captured=self.graph is not None)
+        if new is old:                 # nothing read (always so at d <= 16)
             return
-        before = (self.blocked > 0, bool(self.staged))
-        from .device import OPT_BLOCKED, OPT_ML_UNSTAGED, OPT_SCREEN, OPT_SM_LANES, OPT_STAGED_REDRAW
-        opts = getattr(self, "_opts", None) or RegimeOptions.from_env()
-        if opts.pin == "screened" and self.staged:
-            return                     # pinned to the screened batches (RegimeOptions.pin)
-        walker_ok = opts.walker_ok
-        nd = self.ctx.n_dim
-        screened = opts.screen and nd <= 112
-        up_est, down_true, cap, floor = regime_band("screened" if screened else "walker", nd)
-        multi_ok = screened and self.K <= 64 and opts.blk_mfma
-        if self.K != 1:
-            sm_ = REGIME_THRESHOLDS["several_modes"]
-            want_blk = multi_ok and mean_attempts < (sm_["down"] if self.blocked else sm_["up"])
-        elif self.blocked:             # geometric estimate
-            want_blk = mean_attempts < up_est or not walker_ok
-        else:                          # true mean (screened batches / row walker, or the multi-lane kernel of a run's first steps)
-            want_blk = mean_attempts < down_true and (walker_ok or mean_attempts < 2.0)
-        # redraw-dominated steps: the screened batches -- with several modes one mode after the other over the particles of each
-        # (propose_mf.hip: tph_propose_mf_modes); the multi-lane kernel only where the screen is off or K > 64
-        want_sm = (self.K == 1 or multi_ok) and not want_blk and walker_ok
-        self._since = getattr(self, "_since", 1 << 30) + 1
-        self._dwell = getattr(self, "_dwell", 0)
-        if (want_blk, want_sm) == before:
-            if self.graph is not None:
-                return                 # same kernel: the graph stays (its rounds and lane groups too)
-        else:
-            dw = REGIME_THRESHOLDS["dwell"]
-            if self._since <= self._dwell:
-                return                 # a switch so soon after the last one: wait (the current kernel is correct, only not the fastest)
-            # consecutive switches each within a few readings of the one before: the second is still free (a run that crosses a
-            # band once each way), from the third on the wait doubles
-            self._quick = getattr(self, "_quick", 0) + 1 if self._since < max(dw["recent"], 2 * self._dwell) else 0
-            self._dwell = 0 if self._quick < 2 else min(dw["max"], dw["first"] << (self._quick - 2))
-            self._since = 0
-        rounds = 0
-        if want_blk:
-            # A round that still has work costs at least one tile's latency (30-45 us at 100-D) however short its list: rounds
-            # pay while the list fills the chip.  Expected list after k rounds: n (1 - 1/m)^k.  Measured against one round +
-            # stragglers: 262 144 x 32-D -20 ... -26 %, 131 072 x 100-D -12 ... -17 %, 65 536 x 50-D +-0 (lists too short).
-            # (screened: the straggler pass is a screened launch over the list: it settles a short list in one launch's latency, a
-            # long one at ~8 us per straggler and wave -- rounds pay while the expected list is more than a few hundred particles)
-            f, left = max(0.0, 1.0 - 1.0 / mean_attempts), float(self.n)
-            rounds = 1
-            # (a matrix-core round gives its failing columns `tries` attempts in place: TPH_OPT_BLK_TRIES, 2 up to n_dim 32, 1 above)
-            f_round = f ** (1 if (nd > 32 or not screened) else 2)
-            fan, fan_div = screened and opts.fan != 0, {2: 1, 3: 4}.get(opts.fan, 2)
-            left *= f_round                         # after round 0
-            while rounds < cap and left >= floor:
-                # a list round gives every listed particle G attempts side by side (TPH_OPT_BLK_FAN, propose_blkm.hip: the largest
-                # power of two <= 16 with G x list <= n / 2), so the list shrinks by f_round ** G
-                G = 1
-                while fan and G < 16 and 2 * fan_div * G * left <= self.n:
-                    G *= 2
-                left *= f_round ** G
-                rounds += 1
-        if rounds != self.blocked:
-            self.blocked = rounds
-            self.ctx.set_option(OPT_BLOCKED, rounds)
-            from .device import OPT_BLK_FAN
-            self.ctx.set_option(OPT_BLK_FAN, opts.fan)
-        lanes = opts.sm_lanes          # 0: the library sizes the lane groups (8 or 16 lanes per particle)
-        if want_sm != self.staged or lanes != self.sm_lanes:
-            self.staged, self.sm_lanes = want_sm, lanes
-            self.ctx.set_option(OPT_STAGED_REDRAW, 1 if want_sm else 0)
-            self.ctx.set_option(OPT_SM_LANES, lanes)
-            self.ctx.set_option(OPT_SCREEN, 1 if screened else 0)
-        un = REGIME_THRESHOLDS["unstaged"]
-        want = mean_attempts > (un["down"] if self.unstaged else un["up"])      # hysteresis
-        if want != self.unstaged and self.graph is None:
-            self.unstaged = want
-            self.ctx.set_option(OPT_ML_UNSTAGED, 1 if want else 0)
-        if self.graph is not None and (self.blocked > 0, bool(self.staged)) != before:
+        if new[:4] != old[:4]:
+            self._push_options()
+        if self.graph is not None and new.kernel != old.kernel:
             # retired, not destroyed: its last replay may still be in flight (and its pool holds the callbacks' outputs)
             self._retired_graphs.append((self.graph, self._keep))
             self.graph, self._keep = None, None
@@ -527,6 +376,7 @@ class DeviceMCMC:
         return (tensor, blobs); the evolved array is left in `self.blobs`.
         Returns (efficiency, acceptance, iterations, n_calls) like mcmc.py:196-208."""
         import torch
+        from .device import KERNEL_ID
         self.blobs = None if blobs is None else np.array(blobs, copy=True)
         if blobs is not None and (self.engines is not None or self.plugin is not None):
             raise ValueError("blobs follow the step-by-step path (host callbacks): engines and plugin must be None")
@@ -564,7 +414,7 @@ class DeviceMCMC:
             speculated = False
             calls += n_global
             if self.plugin is not None and self.plugin.can_fuse_accept(n):   # callbacks compiled into the Metropolis kernel
-                from .device import KERNEL_ID                                 # (hipcallbacks.py; not where its sum over data is split)
+                # (hipcallbacks.py; not where its sum over data is split)
                 self.plugin.accept(KERNEL_ID[self.kernel], self.beta, u, x, logl, up, maha_u, maha_up, assign, K,
                                    modes.dof_dev, self.rng.seed, self.rng.next(), self.item0, None, partials=partials)
             else:
@@ -594,16 +444,17 @@ class DeviceMCMC:
                 speculated = True
                 ev.synchronize()
                 st = state_host.numpy().copy()
-                if self.pbar is not None and self.verbose:
-                    self.pbar.update_stats({"calls": self.pbar.info.get("calls", 0) + n_global, "acc": st[3],
-                                            "steps": it, "eff": st[4]})
+                self._progress(n_global, st, it)
                 if st[1] != 0.0:
                     break
         return float(st[4]), float(st[3]), it, calls
 
+    def _progress(self, calls, st, steps):
+        """Step record `st` to the progress bar, with `calls` more likelihood calls."""
+        if self.pbar is not None and self.verbose:
+            self.pbar.update_stats({"calls": self.pbar.info.get("calls", 0) + calls, "acc": st[3], "steps": steps, "eff": st[4]})
 
     def _run_engine(self, u, x, logl, assign, K, n, n_global, sig0, counts):
-        import torch
         ctx, d = self.ctx, self.ctx.n_dim
         active = self.comm is not None and self.comm.active
         if active:
@@ -626,9 +477,7 @@ class DeviceMCMC:
             st = eng.run_all()                # every step of the run in one launch (None: refused, nothing ran)
             if st is not None:
                 it = int(st[0])
-                if self.pbar is not None and self.verbose:
-                    self.pbar.update_stats({"calls": self.pbar.info.get("calls", 0) + it * n_global, "acc": st[3],
-                                            "steps": it, "eff": st[4]})
+                self._progress(it * n_global, st, it)
         if st is None:
             eng.step(self.comm)
         while st is None or st[1] == 0.0:
@@ -639,9 +488,7 @@ class DeviceMCMC:
                     eng.wait_record(2)        # first run of this engine: learn the proposal kernel's regime after two steps
             else:                             # the rule cannot fire earlier (mcmc.py:119-131)
                 st = eng.wait_record(it)
-                if self.pbar is not None and self.verbose:
-                    self.pbar.update_stats({"calls": self.pbar.info.get("calls", 0) + n_global, "acc": st[3],
-                                            "steps": it, "eff": st[4]})
+                self._progress(n_global, st, it)
                 if st[1] != 0.0:
                     break
         if eng.u is not u:                    # graph mode: the step worked on the engine's fixed-address buffers

@@ -81,35 +81,62 @@ def test_history_sized_temporaries_come_from_buckets():
     assert "bit_length" in src and "3 // 4" in src
 
 
-def test_proposal_regime_rule_d_gt_16(monkeypatch):
-    """(With the screen off, TEMPEST_AMD_SCREEN=0: the FP64 row walker's crossovers; the screened rule: next test.)
-    StepEngine._regime (mcmc.py): which d > 16 proposal kernel the NEXT steps get from the redraw probe -- blocked kernel in
-    R rounds for a few attempts per particle (R from the expected length of the round's list), row walker when redraws
-    dominate, one threshold per direction (the blocked path reports the geometric estimate, the walker the true mean), the
-    multi-lane kernel for several modes; a captured graph keeps what it was captured with until the rule asks for another
-    kernel."""
+class _Rule:
+    """The regime rule alone: Regime.next over the readings of one engine shape.  `fresh`: every reading as if the last switch were
+    long ago (the thresholds without the dwell)."""
+
+    def __init__(self, d, n, K=1, opts=None, fresh=False):
+        from tempest_amd.regime import Regime, RegimeOptions
+        self.shape = dict(n_dim=d, n=n, K=K, opts=opts or RegimeOptions())
+        self.regime, self.fresh = Regime(), fresh
+
+    def read(self, mean_attempts, captured=False):
+        if self.fresh:
+            self.regime = self.regime._replace(since=1 << 30, dwell=0, quick=0)
+        self.regime = self.regime.next(mean_attempts, captured=captured, **self.shape)
+
+    blocked, staged, unstaged = (property(lambda self, f=f: getattr(self.regime, f)) for f in ("blocked", "staged", "unstaged"))
+
+
+def _engine(d, n, K=1, opts=None, fresh=False):
+    """What is the engine's of a reading: the regime's options in the context and the retirement of a captured graph."""
     from tempest_amd import mcmc
-    from tempest_amd.device import OPT_BLOCKED, OPT_ML_UNSTAGED, OPT_SCREEN, OPT_STAGED_REDRAW
-    monkeypatch.setenv("TEMPEST_AMD_SCREEN", "0")
 
     class Ctx:
-        def __init__(self, d):
-            self.n_dim, self.opts = d, {}
+        n_dim = d
+
+        def __init__(self):
+            self.opts = {}
 
         def set_option(self, k, v):
             self.opts[k] = v
 
-    class Eng:
-        def _regime(self, m):          # the thresholds alone: every reading as if the last switch were long ago (the dwell: last test)
-            self._since, self._dwell, self._quick = 1 << 30, 0, 0
-            return mcmc.StepEngine._regime(self, m)
+    class Eng(mcmc.StepEngine):
+        def __init__(self):
+            self.ctx, self.n, self.K, self.graph, self._keep, self._retired_graphs = Ctx(), n, K, None, None, []
+            self._opts, self.regime = opts or mcmc.RegimeOptions(), mcmc.Regime()
 
-        def __init__(self, d, n, K=1):
-            self.ctx, self.n, self.K, self.graph = Ctx(d), n, K, None
-            self.blocked, self.staged, self.sm_lanes, self.unstaged = 0, False, 0, False
-            self._retired_graphs, self._keep = [], None
+        def _regime(self, m):
+            if fresh:
+                self.regime = self.regime._replace(since=1 << 30, dwell=0, quick=0)
+            mcmc.StepEngine._regime(self, m)
+    return Eng()
 
-    e = Eng(50, 65536)
+
+def test_proposal_regime_rule_d_gt_16():
+    """(With the screen off, TEMPEST_AMD_SCREEN=0: the FP64 row walker's crossovers; the screened rule: second half.)
+    Regime.next (regime.py): which d > 16 proposal kernel the NEXT steps get from the redraw probe -- blocked kernel in
+    R rounds for a few attempts per particle (R from the expected length of the round's list), row walker when redraws
+    dominate, one threshold per direction (the blocked path reports the geometric estimate, the walker the true mean), the
+    multi-lane kernel for several modes; StepEngine._regime puts the regime into the context, and a captured graph keeps what it
+    was captured with until the rule asks for another kernel.  (Every reading as if the last switch were long ago; the dwell:
+    next test.)"""
+    from tempest_amd import mcmc
+    from tempest_amd.device import OPT_BLOCKED, OPT_ML_UNSTAGED, OPT_SCREEN, OPT_STAGED_REDRAW
+    off = mcmc.RegimeOptions.from_env({"TEMPEST_AMD_SCREEN": "0"})
+    assert not off.screen and mcmc.RegimeOptions.from_env({}).screen
+
+    e = _engine(50, 65536, opts=off, fresh=True)
     e._regime(60.0)                                   # first steps of a run from the prior: redraws dominate
     assert e.staged and e.blocked == 0 and e.ctx.opts[OPT_STAGED_REDRAW] == 1 and e.ctx.opts.get(OPT_BLOCKED, 0) == 0
     e._regime(6.0)                                    # the walker's probe is the TRUE mean: it keeps the step down to 5
@@ -132,26 +159,26 @@ def test_proposal_regime_rule_d_gt_16(monkeypatch):
     e._regime(60.0)
     assert e.graph is g and len(e._retired_graphs) == 1
     # many particles: rounds while the expected list fills the chip, at most 24
-    big = Eng(32, 262144)
+    big = _engine(32, 262144, opts=off, fresh=True)
     big._regime(2.27)
     assert big.blocked == 5 and big.ctx.opts[OPT_BLOCKED] == 5
-    big.blocked = 1
+    big.regime = big.regime._replace(blocked=1)
     big._regime(3.4)
     assert 5 < big.blocked <= 24
     # n_dim >= 64: the crossovers sit higher (estimate 4.5, true mean 8)
-    wide = Eng(100, 131072)
-    wide._regime(7.0)
+    wide = _Rule(100, 131072, opts=off, fresh=True)
+    wide.read(7.0)
     assert wide.blocked >= 1 and not wide.staged
-    wide._regime(4.4)
+    wide.read(4.4)
     assert wide.blocked >= 1
-    wide._regime(4.6)
+    wide.read(4.6)
     assert wide.staged and wide.blocked == 0
-    wide._regime(8.5)
+    wide.read(8.5)
     assert wide.staged
-    wide._regime(7.9)
+    wide.read(7.9)
     assert wide.blocked >= 1 and not wide.staged
     # several modes: neither; the multi-lane kernel, un-staged while redraws dominate (hysteresis 8 / 4)
-    k4 = Eng(32, 262144, K=4)
+    k4 = _engine(32, 262144, K=4, opts=off, fresh=True)
     k4._regime(20.0)
     assert k4.blocked == 0 and not k4.staged and k4.unstaged and k4.ctx.opts[OPT_ML_UNSTAGED] == 1
     k4._regime(5.0)
@@ -159,14 +186,13 @@ def test_proposal_regime_rule_d_gt_16(monkeypatch):
     k4._regime(3.0)
     assert not k4.unstaged
     # d <= 16 has one kernel
-    small = Eng(10, 1 << 20)
+    small = _engine(10, 1 << 20, opts=off, fresh=True)
     small._regime(3.0)
     assert small.ctx.opts == {}
-    monkeypatch.setenv("TEMPEST_AMD_SCREEN", "1")
     # ---- with the screened batches (default): their time is flat in the attempt count, so the crossovers sit lower at high
     # n_dim and higher at 32-D (tools/regime_sweep.py), and the blocked kernel runs more, shorter rounds (the straggler pass is
     # a screened launch over the list)
-    s100 = Eng(100, 131072)
+    s100 = _engine(100, 131072, fresh=True)
     s100._regime(60.0)
     assert s100.staged and s100.blocked == 0 and s100.ctx.opts[OPT_SCREEN] == 1
     s100._regime(5.1)
@@ -177,46 +203,46 @@ def test_proposal_regime_rule_d_gt_16(monkeypatch):
     assert not s100.staged and s100.blocked == 6
     s100._regime(3.1)
     assert s100.staged and s100.blocked == 0
-    s50 = Eng(50, 65536)                             # 33..63-D, with the list rounds fanned out: estimate 3.4 / true mean 5.5
-    s50._regime(30.0)
+    s50 = _Rule(50, 65536, fresh=True)                # 33..63-D, with the list rounds fanned out: estimate 3.4 / true mean 5.5
+    s50.read(30.0)
     assert s50.staged and s50.blocked == 0
-    s50._regime(5.6)
+    s50.read(5.6)
     assert s50.staged
-    s50._regime(5.4)
+    s50.read(5.4)
     assert not s50.staged and 2 <= s50.blocked <= 8
-    s50._regime(3.3)
+    s50.read(3.3)
     assert not s50.staged and s50.blocked >= 2
-    s50._regime(3.5)
+    s50.read(3.5)
     assert s50.staged and s50.blocked == 0
-    s50._regime(1.3)                                  # one try per round above 32-D; a fanned-out second round empties the list
+    s50.read(1.3)                                     # one try per round above 32-D; a fanned-out second round empties the list
     assert not s50.staged and 2 <= s50.blocked <= 4
-    s32 = Eng(32, 262144)
-    s32._regime(14.0)
+    s32 = _Rule(32, 262144, fresh=True)
+    s32.read(14.0)
     assert s32.staged
-    s32._regime(12.0)                                 # 32-D: the screened batches only win above ~13 attempts per particle
+    s32.read(12.0)                                    # 32-D: the screened batches only win above ~13 attempts per particle
     assert not s32.staged and s32.blocked == 12
-    s32._regime(1.05)                                 # two attempts per round in place: lists 594, 1: two rounds
+    s32.read(1.05)                                    # two attempts per round in place: lists 594, 1: two rounds
     assert s32.blocked == 2
-    s32._regime(8.1)
+    s32.read(8.1)
     assert s32.staged
     # several modes: the matrix-core rounds over mode-pure tiles below ~8 estimated attempts, the screened batches mode by mode
-    # above (round 5; the multi-lane kernel only with the screen off: previous test)
-    m4 = Eng(32, 262144, K=4)
-    m4._regime(20.0)
+    # above (round 5; the multi-lane kernel only with the screen off: first half)
+    m4 = _Rule(32, 262144, K=4, fresh=True)
+    m4.read(20.0)
     assert m4.blocked == 0 and m4.staged
-    m4._regime(12.0)
+    m4.read(12.0)
     assert m4.blocked == 12 and not m4.staged
-    m4._regime(1.2)
+    m4.read(1.2)
     assert 2 <= m4.blocked <= 4 and not m4.staged
-    m4._regime(8.5)
+    m4.read(8.5)
     assert m4.blocked == 0 and m4.staged
-    m80 = Eng(32, 262144, K=80)                        # more modes than the mode tables hold: the multi-lane kernel
-    m80._regime(20.0)
+    m80 = _Rule(32, 262144, K=80, fresh=True)          # more modes than the mode tables hold: the multi-lane kernel
+    m80.read(20.0)
     assert m80.blocked == 0 and not m80.staged and m80.unstaged
 
 
 def test_regime_rule_does_not_oscillate(monkeypatch):
-    """a redraw probe that sits on a threshold of StepEngine._regime and crosses it at every reading (the blocked
+    """a redraw probe that sits on a threshold of the regime rule and crosses it at every reading (the blocked
     rounds report the geometric estimate, the screened batches the true mean: 3.1 >= 3.0 sends the step to the batches, whose 4.9 <
     5.0 sends it back) must not retire and re-capture the step's graph at every step: after two free switches the next ones wait
     4, 8, ... 64 readings.  Each threshold crossed ONCE, in either direction, switches at once; the debugging switches are read
@@ -224,41 +250,24 @@ def test_regime_rule_does_not_oscillate(monkeypatch):
     from tempest_amd import mcmc
     for var in ("TEMPEST_AMD_SCREEN", "TEMPEST_AMD_STAGED", "TEMPEST_AMD_BLK_MFMA", "TEMPEST_AMD_BLK_FAN", "TEMPEST_AMD_SM_LANES"):
         monkeypatch.delenv(var, raising=False)
-
-    class Ctx:
-        def __init__(self, d):
-            self.n_dim, self.opts, self.calls = d, {}, 0
-
-        def set_option(self, k, v):
-            self.opts[k] = v
-            self.calls += 1
-
-    class Eng:
-        _regime = mcmc.StepEngine._regime
-
-        def __init__(self, d, n, K=1):
-            self.ctx, self.n, self.K, self.graph = Ctx(d), n, K, None
-            self.blocked, self.staged, self.sm_lanes, self.unstaged = 0, False, 0, False
-            self._retired_graphs, self._keep = [], None
-            self._opts = mcmc.RegimeOptions.from_env()
-            self._since, self._dwell, self._quick = 1 << 30, 0, 0
+    opts = mcmc.RegimeOptions.from_env()
 
     for d, n in ((100, 131072), (50, 65536), (32, 262144)):
         up, down, _, _ = mcmc.regime_band("screened", d)
         # one crossing each way switches immediately, in both directions, at exactly the tabulated numbers
-        e = Eng(d, n)
-        e._regime(60.0)
-        assert e.staged and not e.blocked
-        e._regime(down + 0.01)
-        assert e.staged
-        e._regime(down - 0.01)
-        assert e.blocked >= 1 and not e.staged
-        e._regime(up - 0.01)
-        assert e.blocked >= 1
-        e._regime(up + 0.01)
-        assert e.staged and not e.blocked
+        r = _Rule(d, n, opts=opts)
+        r.read(60.0)
+        assert r.staged and not r.blocked
+        r.read(down + 0.01)
+        assert r.staged
+        r.read(down - 0.01)
+        assert r.blocked >= 1 and not r.staged
+        r.read(up - 0.01)
+        assert r.blocked >= 1
+        r.read(up + 0.01)
+        assert r.staged and not r.blocked
         # the probe flips at every reading: count the kernel switches (= graph retirements) over 400 readings
-        e = Eng(d, n)
+        e = _engine(d, n, opts=opts)
         e._regime(60.0)
         switches, kinds = 0, []
         for _ in range(400):
@@ -282,24 +291,55 @@ def test_regime_rule_does_not_oscillate(monkeypatch):
         assert e.staged and not e.blocked
     # several modes: the same with the two-sided band of the matrix-core rounds
     sm = mcmc.REGIME_THRESHOLDS["several_modes"]
-    e = Eng(32, 262144, K=4)
-    e._regime(20.0)
-    assert not e.blocked
+    r = _Rule(32, 262144, K=4, opts=opts)
+    r.read(20.0)
+    assert not r.blocked
     switches = 0
     for _ in range(400):
-        was = e.blocked > 0
-        e._regime(sm["up"] - 0.01 if not e.blocked else sm["down"] + 0.01)
-        switches += (e.blocked > 0) != was
+        was = r.blocked > 0
+        r.read(sm["up"] - 0.01 if not r.blocked else sm["down"] + 0.01)
+        switches += (r.blocked > 0) != was
     assert switches <= 12
     # the environment is not consulted per step: a switch flipped AFTER construction changes nothing for this engine
-    e = Eng(50, 65536)
+    e = _engine(50, 65536, opts=mcmc.RegimeOptions.from_env())
     monkeypatch.setenv("TEMPEST_AMD_SCREEN", "0")
     e._regime(6.0)                                  # screened band of 50-D: 6.0 >= 5.5 keeps the batches; the walker band (5.0) too
     e._regime(5.2)                                  # screened: 5.2 < 5.5 -> blocked rounds; with the screen off it would have stayed
     assert e.blocked >= 1
+
+
+def test_regime_module_needs_neither_the_environment_nor_torch():
+    """The rule is a function of its arguments: tempest_amd/regime.py imports nothing but typing at module level -- no os, no torch,
+    no device.py -- and only RegimeOptions.from_env, called when an engine is built, looks at the environment."""
+    import ast
     import inspect
-    src = inspect.getsource(mcmc.StepEngine._regime)
-    assert "os.environ" not in src and "import os" not in src
+    from tempest_amd import regime
+    tree = ast.parse(inspect.getsource(regime))
+    imported = {a.name if isinstance(node, ast.Import) else node.module
+                for node in tree.body if isinstance(node, (ast.Import, ast.ImportFrom)) for a in node.names}
+    assert imported == {"typing"}
+    assert not hasattr(regime, "os") and not hasattr(regime, "torch") and not hasattr(regime, "device")
+    nested = {node.module for node in ast.walk(tree) if isinstance(node, ast.ImportFrom)} | {
+        a.name for node in ast.walk(tree) if isinstance(node, ast.Import) for a in node.names}
+    assert nested == {"typing", "os"}
+    for fn in (regime.Regime.next, regime.Regime.initial, regime.Regime.options, regime.regime_band):
+        assert not {"os", "environ", "getenv"} & set(inspect.unwrap(getattr(fn, "__func__", fn)).__code__.co_names)
+
+
+@pytest.mark.parametrize("d", [16, 17, 112, 113])
+@pytest.mark.parametrize("K", [1, 4, 64, 65])
+def test_regime_initial_truth_table(d, K):
+    """An engine's first steps run as screened batches exactly where the screened kernel exists for its shape and may be used:
+    16 < d <= 112 with the screen and the walker switches on, and one mode without an assignment or 2..64 modes with one."""
+    from tempest_amd.regime import Regime, RegimeOptions
+    for has_assign in (False, True):
+        for screen in (False, True):
+            for walker_ok in (False, True):
+                r = Regime.initial(d, K, has_assign, RegimeOptions(walker_ok=walker_ok, screen=screen))
+                want = (d > 16 and (screen and d <= 112) and walker_ok
+                        and ((K == 1 and not has_assign) or (1 < K <= 64 and has_assign)))
+                assert r.staged is bool(want), (d, K, has_assign, screen, walker_ok)
+                assert r == Regime(staged=bool(want)) and (r.blocked, r.sm_lanes, r.unstaged, r.dwell, r.quick) == (0, 0, False, 0, 0)
 
 
 def test_virtual_shards_of_the_canonical_partition():

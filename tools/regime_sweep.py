@@ -1,4 +1,4 @@
-"""Which d > 16 proposal path is fastest at which redraw rate: the table behind StepEngine._regime (tempest_amd/mcmc.py).
+"""Which d > 16 proposal path is fastest at which redraw rate: the table behind Regime.next (tempest_amd/regime.py).
 
     python tools/regime_sweep.py [--sizes 65536x50,131072x100,262144x32] [--kernel tpcn] [--reps 7]
 

@@ -349,13 +349,15 @@ def metropolis_alpha(beta, logl, logl_prime, factor):
 
 
 def adapt_sigma_tpcn(sigma, mean_accept, iteration, sigma_0):
-    """mcmc.py:281-288."""
-    return float(np.clip(sigma + (mean_accept - 0.234) / (iteration + 1), 0, min(sigma_0, 0.99)))
+    """mcmc.py:281-288 (the rate is formed first and multiplied, as there: one rounding more than a division)."""
+    rate = 1.0 / (iteration + 1)
+    return float(np.clip(sigma + rate * (mean_accept - 0.234), 0, min(sigma_0, 0.99)))
 
 
 def adapt_sigma_rwm(sigma, mean_accept, iteration):
     """mcmc.py:320-323."""
-    return sigma + (mean_accept - 0.234) / (iteration + 1)
+    rate = 1.0 / (iteration + 1)
+    return sigma + rate * (mean_accept - 0.234)
 
 
 def adaptive_steps(n_steps, n_max, n_dim, sigmas, assignments, n_clusters, current_acceptance):

@@ -516,13 +516,15 @@ __device__ inline void tph_adapt_scalar(int kernel, const double* __restrict__ s
 }
 
 // tpCN's proposal-density ratio in the Metropolis factor (mcmc.py:251-279): -A + B with A, B = -1/2 (d + nu) log(1 + m / nu) at
-// u' and u.  The lean log (both arguments are >= 1 for finite forms); a NaN / inf form goes through the library log so that
-// alpha stays NaN -> 0 as in the reference.  One definition for k_accept and the HIP-callback plugins (bit-identical paths).
+// u' and u.  The lean log and division (both arguments are >= 1 for finite forms); a NaN / inf / >= 1e300 nu form goes through
+// the library log AND the IEEE division -- the lean division makes inf - inf = NaN of an infinite form, where the reference has
+// log(inf): an infinite form at u' alone gives alpha = 1, at u alone 0, at both NaN -> 0.  One definition for k_accept and the
+// HIP-callback plugins (bit-identical paths).
 __device__ __forceinline__ double tph_tpcn_factor(double d_plus_nu, double nu, double m_u, double m_up) {
   const double au = 1.0 + tph_div(m_u, nu), ap = 1.0 + tph_div(m_up, nu);
   const bool plain = au < 1e300 && ap < 1e300;
-  const double B = -0.5 * d_plus_nu * (plain ? tph_log(au) : log(au));
-  const double A = -0.5 * d_plus_nu * (plain ? tph_log(ap) : log(ap));
+  const double B = -0.5 * d_plus_nu * (plain ? tph_log(au) : log(1.0 + m_u / nu));
+  const double A = -0.5 * d_plus_nu * (plain ? tph_log(ap) : log(1.0 + m_up / nu));
   return -A + B;
 }
 

@@ -16,7 +16,7 @@ import math
 
 import numpy as np
 
-from .trace import _EMITTED, _QUANTILE, TV, emit, quantile_header, trace_function
+from .trace import TV, emit_function, quantile_header, trace_function
 
 DEVICE_HELPERS = quantile_header()
 _LOG_SQRT_2PI = 0.5 * math.log(2.0 * math.pi)
@@ -244,6 +244,5 @@ class Prior:
         """`__device__ void prior_transform(const double* u, double* x)` as trace_callbacks(prior.transform, ...) emits it, behind
         the text of csrc/quantile.h where a column needs it: to go in front of a hand-written log_likelihood."""
         g = trace_function(self.transform, self.n_dim, self.n_dim, "prior_transform")
-        signature, arg, store = _EMITTED["prior_transform"]
-        parts = [DEVICE_HELPERS.rstrip("\n")] if any(g.nodes[i][0] in _QUANTILE for i in g.live()) else []
-        return "\n".join(parts + [emit(g, f"__device__ {signature})", arg, store)]) + "\n"
+        parts = [DEVICE_HELPERS.rstrip("\n")] if g.needs_quantile_header() else []
+        return "\n".join(parts + [emit_function(g, "prior_transform")]) + "\n"

@@ -326,7 +326,7 @@ __device__ __forceinline__ double tph_logaddexp(double x, double y) {
   double t = x - y;
   if (t > 0) return x + tph_log1p_unit(exp(-t));
   if (t <= 0) return y + tph_log1p_unit(exp(t));
-  return t;  // NaN
+  return x + y;  // NaN, with the sign NumPy's x - y has: the compiler forms t as x + (-y), which turns the sign of a NaN in y
 }
 
 // ---- Philox4x32-10 (twin of oracle/philox.py) ----

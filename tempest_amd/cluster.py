@@ -21,8 +21,8 @@ from typing import Optional
 import numpy as np
 
 from ._philox_host import uniform_scalar
+from .device import TAG_CLUSTER
 
-TAG_CLUSTER = 9
 LOG2PI = math.log(2.0 * math.pi)
 
 

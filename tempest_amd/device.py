@@ -13,32 +13,17 @@ import torch
 from . import _lib
 from ._lib import check
 
-KERNEL_ID = {"tpcn": 0, "rwm": 1}
-KEY_U, KEY_X, KEY_LOGL, KEY_LOGMIX = 0, 1, 2, 3
-STEP_STATE_LEN = 10            # TPH_STEP_STATE_LEN
-OPT_ML_UNSTAGED = 3            # TPH_OPT_ML_UNSTAGED
-OPT_BLOCKED = 4                # TPH_OPT_BLOCKED
-OPT_MODES_EPOCH = 5            # TPH_OPT_MODES_EPOCH
-OPT_ROW_MIRROR = 6             # TPH_OPT_ROW_MIRROR
-OPT_COV_KERNEL = 7             # TPH_OPT_COV_KERNEL
-OPT_SORTED_DRAWS = 8           # TPH_OPT_SORTED_DRAWS
-OPT_STAGED_REDRAW = 9          # TPH_OPT_STAGED_REDRAW
-OPT_SM_LANES = 10              # TPH_OPT_SM_LANES
-OPT_SM_THRESHOLD = 11          # TPH_OPT_SM_THRESHOLD
-OPT_SCREEN = 12                # TPH_OPT_SCREEN
-OPT_MF_LANES = 13              # TPH_OPT_MF_LANES
-OPT_MF_AUDIT = 14              # TPH_OPT_MF_AUDIT
-OPT_BLK_MFMA = 15              # TPH_OPT_BLK_MFMA
-OPT_BLK_TRIES = 16             # TPH_OPT_BLK_TRIES
-OPT_BLK_FAN = 17               # TPH_OPT_BLK_FAN
-OPT_HISTORY_VM = 18            # TPH_OPT_HISTORY_VM
-OPT_MF_DEAL = 19               # TPH_OPT_MF_DEAL
-OPT_BLK_STAGE = 20             # TPH_OPT_BLK_STAGE
-OPT_GMM_KERNEL = 21            # TPH_OPT_GMM_KERNEL
-OPT_FORMS_MFMA = 22            # TPH_OPT_FORMS_MFMA
-BC_STRICT, BC_PERIODIC, BC_REFLECTIVE = 0, 1, 2
+# Every `#define TPH_NAME <integer>` of include/tempest_hip.h under the name NAME: OPT_*, KEY_*, BC_*, KERNEL_*, STEP_STATE_LEN,
+# P2P_HANDLE_BYTES, MARGINALS_TILES, VERSION.  Read from the header (_lib.CONSTANTS), so a renumbered option moves with it.
+globals().update((name[len("TPH_"):], value) for name, value in _lib.CONSTANTS.items())
+KERNEL_ID = {"tpcn": KERNEL_TPCN, "rwm": KERNEL_RWM}                # noqa: F821
 
-TAG_PRIOR, TAG_NORMAL, TAG_GAMMA, TAG_ACCEPT, TAG_RESAMPLE, TAG_UPSAMPLE, TAG_REPAIR, TAG_SYST = 1, 2, 3, 4, 5, 6, 7, 8
+# The tag word of the Philox counter: ONE number space over the library (csrc/common.h: TPH_TAG_* = 1 .. 7), the host's own draws
+# (8, 9) and the plugins' replicate() noise (csrc/user_plugin.hip.in: TPHU_TAG_REP_*); oracle/philox.py mirrors 1 .. 9.
+TAG_PRIOR, TAG_NORMAL, TAG_GAMMA, TAG_ACCEPT, TAG_RESAMPLE, TAG_UPSAMPLE, TAG_REPAIR = 1, 2, 3, 4, 5, 6, 7
+TAG_SYST = 8                   # systematic resampling offset (steps/resample.py, sharding.py)
+TAG_CLUSTER = 9                # k-means++ / GMM initialisation (cluster.py)
+TAG_REP_NORMAL, TAG_REP_UNIFORM = 10, 11        # g.normal / g.uniform of a plugin's replicate(x, r, g) (hipcallbacks.py)
 
 
 def _ptr(t, dtype=None):
@@ -219,7 +204,7 @@ class HipContext:
         return out.value
 
     # ------------------------------------------------------------------ small collectives inside the library
-    P2P_HANDLE_BYTES = 64
+    P2P_HANDLE_BYTES = P2P_HANDLE_BYTES
 
     def p2p_export(self) -> bytes:
         """This rank's inbox for the peer-to-peer small-message collectives (tph_comm_p2p_export): a HIP IPC handle."""

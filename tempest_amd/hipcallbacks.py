@@ -36,7 +36,9 @@ from pathlib import Path
 
 import numpy as np
 
-from ._lib import TempestHipError
+from ._cdecl import prototypes
+from ._lib import HEADER_PATH, TempestHipError
+from .device import TAG_REP_NORMAL, TAG_REP_UNIFORM
 
 _CSRC = Path(__file__).resolve().parent / "csrc"
 _TEMPLATE = _CSRC / "user_plugin.hip.in"
@@ -107,9 +109,9 @@ POINTWISE_MAX_TILE = 64            # indices per workgroup, at most (TPHU_PW_RT)
 POINTWISE_MIN_WORKGROUPS = 1024
 POINTWISE_SCRATCH_WORDS = 1 << 23  # 64 MiB of batch scratch at most: more indices than fit go through in batches
 # replicated(): the noise of replicate(x, r, g) is Philox at (item = row, draw = k >> 1, tick = r, tag), these two tags for g.normal /
-# g.uniform (1 .. 9 are taken: csrc/common.h, oracle/philox.py); its sums over rows run in PREDICT_SUM_LAYOUT, discrepancy's sum over
+# g.uniform (the tags are one number space: device.py); its sums over rows run in PREDICT_SUM_LAYOUT, discrepancy's sum over
 # r in SUM_LAYOUT; tiles by predict_tiles.
-REPLICATE_TAGS = (10, 11)
+REPLICATE_TAGS = (TAG_REP_NORMAL, TAG_REP_UNIFORM)
 POINTWISE_KEYS = ("lppd", "mean", "p_waic", "elpd_waic", "elpd_loo", "ess_loo")      # the rows of tphu_pointwise's output
 
 
@@ -312,29 +314,28 @@ def _struct_text(tables) -> str:
     return "\n".join(lines)
 
 
-_PTR, _I64, _INT = C.c_void_p, C.c_int64, C.c_int
 _PREDICT_LAYOUT = PREDICT_SUM_LAYOUT + (PREDICT_MAX_TILE, PREDICT_TABLES)
+# the entry points every plugin has; their prototypes, like those of the parts' entries, are read from the plugin's text (_Parts.bind)
+_ENTRIES = ("tphu_last_error", "tphu_prior", "tphu_like", "tphu_accept", "tphu_step", "tphu_run")
 
 
 # One optional part of a plugin -- everything the host knows about it; a new part is a new row of _PARTS and a field of _Parts.
 # name: the field of _Parts that says whether a plugin has it; mark: its lines of the template, dropped whole without it; define, word:
 # what it adds to the compiler's command line and to the cache key -- present only with the part, so every other source keeps its file
-# name; entry, argtypes: its entry point (a data-carrying plugin takes tphu_data last); report, layout, mismatch: the handshake --
-# tphu_*_layout(i), or one exported function per figure, the tuple they must return [as a function of (n_dim, parts)], and what
-# "does / do not match this package" otherwise.
-_Part = namedtuple("_Part", "name mark define word entry argtypes report layout mismatch", defaults=(None, (), None, None, None))
+# name; entry: its entry point, which the plugin must export; report, layout, mismatch: the handshake -- tphu_*_layout(i), or one
+# exported function per figure, the tuple they must return [as a function of (n_dim, parts)], and what "does / do not match this
+# package" otherwise.
+_Part = namedtuple("_Part", "name mark define word entry report layout mismatch", defaults=(None, None, None, None))
 _PARTS = (
-    _Part("term", "//@T", None, "", "tphu_like_split", (_PTR, _PTR, _I64, _I64, _PTR, _PTR, _I64, _INT)),
-    _Part("n_derived", "//@X", "-DN_DERIVED={n_derived}", "|derived={n_derived}", "tphu_derived", (_PTR, _PTR, _I64, _I64, _PTR, _I64, _INT, _INT),
+    _Part("term", "//@T", None, "", "tphu_like_split"),
+    _Part("n_derived", "//@X", "-DN_DERIVED={n_derived}", "|derived={n_derived}", "tphu_derived",
           ("tphu_n_derived", "tphu_derived_rows"), lambda n_dim, p: (p.n_derived, (derived_tiles(n_dim, p.n_derived) or (0,))[0]),
           "derived() shape or tile rule does"),
     _Part("predict", "//@P", "-DTPHU_PREDICT", "|predict", "tphu_predictive",
-          (_PTR, _PTR, _PTR, _I64, _I64, _PTR, _INT, _PTR, _PTR, _I64, _INT, _I64),
           "tphu_predict_layout", _PREDICT_LAYOUT, "predict() sum layout or tile limits do"),
-    _Part("pointwise", "//@W", "-DTPHU_POINTWISE", "|pointwise", "tphu_pointwise", (_PTR, _PTR, _PTR, _I64, _I64, _PTR, _PTR, _I64, _INT),
+    _Part("pointwise", "//@W", "-DTPHU_POINTWISE", "|pointwise", "tphu_pointwise",
           "tphu_pointwise_layout", PREDICT_SUM_LAYOUT + (POINTWISE_MAX_TILE,), "pointwise sum layout or tile limit does"),
     _Part("replicate", "//@Y", "-DTPHU_REPLICATE", "|replicate", "tphu_replicated",
-          (_PTR, _PTR, _PTR, _I64, _I64, _PTR, _INT, C.c_uint64, _PTR, _INT, _PTR, _PTR, _I64, _INT, _I64),
           "tphu_replicate_layout", _PREDICT_LAYOUT + SUM_LAYOUT + REPLICATE_TAGS, "replicate() sum layouts, tile limits or RNG tags do"),
     _Part("discrepancy", None, "-DTPHU_DISCREPANCY", "|discrepancy"),
 )
@@ -399,29 +400,21 @@ class _Parts(namedtuple("_Parts", "tables term n_derived predict pointwise repli
         """What build_plugin hashes beside the text and the headers: dimension, architecture, flags, toolchain, a word per part."""
         return f"|{n_dim}|{_ARCH}|{' '.join(_FLAGS)}|{_toolchain_id()}" + "".join(part.word.format(**self._asdict()) for part in self.present())
 
-    def bind(self, lib, n_dim: int, path):
-        """Declare the entry points of the loaded plugin and check that it was built for this package's layouts; returns the
-        ctypes type of tphu_data (None without tables)."""
-        lib.tphu_last_error.restype = C.c_char_p
-        u32, dbl = C.c_uint32, C.c_double
-        fns = {"tphu_prior": (_PTR, _PTR, _I64, _I64, _PTR, _I64), "tphu_like": (_PTR, _PTR, _I64, _I64, _PTR),
-               "tphu_accept": (_PTR, _INT, dbl, _PTR, _PTR, _PTR, _PTR, _PTR, _PTR, _PTR, _I64, _I64, _INT, _PTR, C.c_uint64, u32, _I64,
-                               _PTR, _PTR, _PTR, _PTR),
-               "tphu_step": (_PTR, _INT, dbl, _PTR, _PTR, _PTR, _I64, _I64, _PTR, _PTR, _PTR, _PTR, _PTR, _PTR, C.c_uint64, u32, u32, _I64,
-                             _PTR, _PTR, _INT),
-               "tphu_run": (_PTR, _INT, _PTR, _PTR, _PTR, _I64, _I64, _PTR, _PTR, _PTR, _PTR, _PTR, _PTR, C.c_uint64, u32, u32, _I64, _PTR,
-                            _PTR, _PTR, _PTR, dbl, _INT, _INT, _PTR, _INT, _INT, _INT, _INT)}
-        fns.update((part.entry, part.argtypes) for part in self.present() if part.entry)
+    def bind(self, lib, n_dim: int, path, text: str):
+        """Declare the entry points of the loaded plugin from `text`, the translation unit it was compiled from (its extern "C"
+        block says what each takes, the trailing tphu_data pointer of a data-carrying plugin included), and check that it was built
+        for this package's layouts; returns the ctypes type of tphu_data (None without tables)."""
         struct = None
         if self.tables is not None:            # a data-carrying plugin: every entry point takes the host copy of tphu_data last
             fields = [f for name, rank in self.tables for f in
-                      [(name, _PTR)] + ([(name + "_len", _I64)] if rank == 1 else [(name + "_rows", _I64), (name + "_cols", _I64)])]
-            struct = type("tphu_data", (C.Structure,), {"_fields_": fields + [("n_terms", _I64)]})
+                      [(name, C.c_void_p)] + [(name + end, C.c_int64) for end in (("_len",) if rank == 1 else ("_rows", "_cols"))]]
+            struct = type("tphu_data", (C.Structure,), {"_fields_": fields + [("n_terms", C.c_int64)]})
             if lib.tphu_data_abi() != 1 or lib.tphu_data_size() != C.sizeof(struct):
                 raise TempestHipError(f"plugin {path}: data table layout does not match this package")
-        for name, argtypes in fns.items():
+        declared = prototypes(text, "tphu_")
+        for name in _ENTRIES + tuple(part.entry for part in self.present() if part.entry):
             fn = getattr(lib, name)
-            fn.argtypes, fn.restype = list(argtypes) + ([_PTR] if struct is not None else []), _INT
+            fn.restype, fn.argtypes = declared[name]
         if lib.tphu_n_dim() != n_dim:
             raise TempestHipError(f"plugin {path} was built for n_dim={lib.tphu_n_dim()}")
         for part in self.present():            # every exported figure is an int, ctypes' default
@@ -470,7 +463,7 @@ def build_plugin(source: str, n_dim: int, verbose: bool = False, tables=None, te
     only with their part, so every other source keeps the file name it had."""
     parts = _Parts.of(source, tables, term, n_derived, predict, pointwise, replicate, discrepancy)
     text, defs, key = parts.text(source), parts.defines(n_dim), parts.key(n_dim)
-    deps = (_CSRC / "common.h").read_bytes() + (_CSRC.parent.parent / "include" / "tempest_hip.h").read_bytes()
+    deps = (_CSRC / "common.h").read_bytes() + Path(HEADER_PATH).read_bytes()
     tag = hashlib.sha256(text.encode() + deps + key.encode()).hexdigest()[:20]
     name = f"tphu_{n_dim}d_{tag}.so"
     for d in _cache_dirs():
@@ -557,7 +550,7 @@ class HipCallbacks:
         self.path = build_plugin(source, n_dim, verbose, **self.parts.build_args())
         import torch  # noqa: F401  (its HIP runtime must be the one in the process, as for libtempest_hip)
         self.lib = C.CDLL(str(self.path))
-        self._struct_type = self.parts.bind(self.lib, n_dim, self.path)
+        self._struct_type = self.parts.bind(self.lib, n_dim, self.path, self.parts.text(source))
 
     # ---------------------------------------------------------------------------------- data tables
     @property

@@ -6,6 +6,8 @@ from fractions import Fraction
 
 import numpy as np
 
+from ._lib import CONSTANTS
+
 # the order of every floating-point sum over rows: chunks of 64 consecutive rows by the halving tree v[:h] + v[h:2h], blocks of 16
 # chunk sums in chunk order, block sums in block order, every level from +0.0 (PREDICT_SUM_LAYOUT's order)
 MARGINAL_SUM_LAYOUT = (64, 16)
@@ -19,6 +21,7 @@ MARGINAL_SCRATCH_WORDS = 1 << 23   # 64 MiB of batch scratch at most: more colum
 # 4100), rows per workgroup of the 1-D histogram and the select (a multiple of 256), columns per workgroup of the select (tile x
 # n_q <= 16), the 2-D table (1 = global atomics, 2 = LDS, bins_2d <= 64), rows per workgroup of the 2-D histogram, words of batch scratch
 MARGINAL_TILE_KEYS = ("sweep_cols", "hist_cols", "hist_rows", "select_cols", "table_2d", "rows_2d", "batch_words")
+assert len(MARGINAL_TILE_KEYS) == CONSTANTS["TPH_MARGINALS_TILES"]
 DEFAULT_QUANTILES = (0.025, 0.16, 0.5, 0.84, 0.975)
 
 

@@ -1,14 +1,11 @@
 """The C-ABI library loads and exports every symbol include/tempest_hip.h declares (no GPU needed)."""
-import os
-import re
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def declared_symbols():
-    txt = open(os.path.join(ROOT, "include", "tempest_hip.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(tph_[a-z0-9_]+)\s*\(", txt)))
+    from tempest_amd import _lib
+    from tempest_amd._cdecl import prototypes
+    with open(_lib.HEADER_PATH) as f:
+        return sorted(prototypes(f.read(), "tph_"))
 
 
 def test_library_exports_header():
@@ -20,6 +17,7 @@ def test_library_exports_header():
         assert hasattr(lib, n), n
     assert set(names) == set(_lib.SIGNATURES), set(names) ^ set(_lib.SIGNATURES)
     assert lib.tph_version() == 100
+    assert lib.tph_version() == _lib.CONSTANTS["TPH_VERSION"]
 
 
 def test_missing_library_fails_loudly(tmp_path):

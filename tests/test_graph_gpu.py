@@ -9,6 +9,8 @@ import pytest
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
+from tempest_amd.device import OPT_BLOCKED, OPT_MODES_EPOCH, OPT_PROPOSE_VARIANT, OPT_SM_LANES  # noqa: E402
+
 
 @pytest.fixture(scope="module", autouse=True)
 def _need_gpu():
@@ -172,9 +174,9 @@ def test_d_gt_16_proposal_paths_replayed_from_a_graph_equal_eager_launches(kerne
         _, chol, _ = ps.mode_statistics(means, cov)
         return means, chol, np.linalg.inv(chol[0])[None]
     c = HipContext(d, device=0)
-    c.set_option(0, variant)
-    c.set_option(10, 1)
-    c.set_option(4, rounds)
+    c.set_option(OPT_PROPOSE_VARIANT, variant)
+    c.set_option(OPT_SM_LANES, 1)
+    c.set_option(OPT_BLOCKED, rounds)
     m0 = mk_modes(0.29)
     modes = SimpleNamespace(K=1, means_dev=t(m0[0]), chol_dev=t(m0[1]), winv_dev=t(m0[2]), dof_dev=t(np.array([1e6])))
     u, up, mu_, mup = t(rs.rand(d, n)), c.empty(d, n), c.empty(n), c.empty(n)
@@ -201,7 +203,7 @@ def test_d_gt_16_proposal_paths_replayed_from_a_graph_equal_eager_launches(kerne
         modes.means_dev.copy_(t(m[0])); modes.chol_dev.copy_(t(m[1])); modes.winv_dev.copy_(t(m[2]))
         u.copy_(t(np.clip(0.5 + (rs.rand(d, n) - 0.5) * (1.0 if trial < 2 else 0.5), 0.0, 1.0)))
         ctl[0], ctl[7] = float(trial), 10.0 * trial           # steps done (the form at u is carried from trial 1 on), tick base
-        c.set_option(5, 100 + trial)                          # TPH_OPT_MODES_EPOCH: what StepEngine.load() does
+        c.set_option(OPT_MODES_EPOCH, 100 + trial)                          # TPH_OPT_MODES_EPOCH: what StepEngine.load() does
         keep = mu_.clone()
         g.replay()
         torch.cuda.synchronize()

@@ -257,7 +257,7 @@ def test_sources_without_predict_generate_the_parent_text():
 @needs_hipcc
 def test_sources_without_predict_keep_their_file_name():
     from tempest_amd import hipcallbacks as H
-    deps = (H._CSRC / "common.h").read_bytes() + (H._CSRC.parent.parent / "include" / "tempest_hip.h").read_bytes()
+    deps = (H._CSRC / "common.h").read_bytes() + open(H.HEADER_PATH, "rb").read()
     recorded_env = hashlib.sha256(deps + H._toolchain_id().encode()).hexdigest() == PARENT_ENV
     for src, n_dim, tables, term, nder, sha, name in parent_cases():
         got = H.build_plugin(src, n_dim, tables=tables, term=term, n_derived=nder).name

@@ -15,7 +15,10 @@ from oracle import mcmc as omc  # noqa: E402
 from oracle import philox as px  # noqa: E402
 from oracle import ps  # noqa: E402
 
-G = os.path.join(os.path.dirname(__file__), "golden")
+from tempest_amd.device import (OPT_BLK_FAN, OPT_BLK_MFMA, OPT_BLK_STAGE, OPT_BLK_TRIES, OPT_BLOCKED,  # noqa: E402
+                                OPT_PROPOSE_VARIANT, OPT_SM_LANES, OPT_SM_THRESHOLD)
+
+G =os.path.join(os.path.dirname(__file__), "golden")
 
 
 def load(name):
@@ -507,7 +510,7 @@ def test_propose_accept_adapt_vs_oracle(dev, kernel, bc, variant):
     want_up, want_mu, want_mup = omc.propose(kernel, u, assign, means, chol, inv, dof, sigmas, flags, seed, tick, item0)
     c = ctx_for(d)
     # TPH_OPT_PROPOSE_VARIANT: 1 = one-lane LDS kernel, 2 = one-lane register kernel (d<=16), 3 = multi-lane kernel
-    c.set_option(0, {"multilane": 3, "generic": 1, "registers": 2}[variant.split("_")[0]])
+    c.set_option(OPT_PROPOSE_VARIANT, {"multilane": 3, "generic": 1, "registers": 2}[variant.split("_")[0]])
     modes = _Modes(means, chol, inv, dof, dev)
     up, mu_, mup = c.empty(d, n), c.empty(n), c.empty(n)
     ut = soa(u, dev)
@@ -733,7 +736,7 @@ def test_deferred_metropolis_update_equals_in_place(dev, kernel, variant):
     assign = rs.randint(K, size=n).astype(np.int32)
     u0 = np.clip(means[assign] + 0.15 * rs.randn(n, d), 0.01, 0.99)
     c = ctx_for(d)
-    c.set_option(0, {"multilane": 3, "generic": 1, "registers": 2}[variant.split("_")[0]])
+    c.set_option(OPT_PROPOSE_VARIANT, {"multilane": 3, "generic": 1, "registers": 2}[variant.split("_")[0]])
     modes = _Modes(means, chol, inv, dof, dev)
     at, st = torch.from_numpy(assign).to(dev), torch.from_numpy(sigmas).to(dev)
 
@@ -827,16 +830,16 @@ def test_blocked_proposal_kernel_vs_oracle_and_multilane(dev, kernel, bc, d, rou
     got = {}
     for variant in (4, 3):
         c = ctx_for(d)
-        c.set_option(0, variant)
-        c.set_option(4, rounds if variant == 4 else 0)
-        c.set_option(15, mfma)                 # TPH_OPT_BLK_MFMA
-        c.set_option(16, tries)                # TPH_OPT_BLK_TRIES: attempts per round, in place (matrix-core kernel)
+        c.set_option(OPT_PROPOSE_VARIANT, variant)
+        c.set_option(OPT_BLOCKED, rounds if variant == 4 else 0)
+        c.set_option(OPT_BLK_MFMA, mfma)                 # TPH_OPT_BLK_MFMA
+        c.set_option(OPT_BLK_TRIES, tries)                # TPH_OPT_BLK_TRIES: attempts per round, in place (matrix-core kernel)
         up, mu_, mup = c.empty(d, n), c.empty(n), c.empty(n)
         state = c.zeros(10)
         c.propose(kernel, soa(u, dev), None, modes, st, ft, seed, tick, item0, up, mu_, mup, ctl=state)
         got[variant] = (aos(up), mu_.cpu().numpy(), mup.cpu().numpy(), state.cpu().numpy())
-        c.set_option(4, 0)
-        c.set_option(15, 1)
+        c.set_option(OPT_BLOCKED, 0)
+        c.set_option(OPT_BLK_MFMA, 1)
     np.testing.assert_allclose(got[4][0], want_up, rtol=1e-11, atol=1e-13)
     np.testing.assert_allclose(got[4][0], got[3][0], rtol=1e-11, atol=1e-13)
     strict = np.nonzero(flags == 0)[0]
@@ -880,12 +883,12 @@ def test_blocked_list_rounds_fan_out(dev, kernel, d, rounds, tries, spread, n):
     got = {}
     c = ctx_for(d)
     for fan in (1, 0):
-        c.set_option(0, 4); c.set_option(4, rounds); c.set_option(15, 1); c.set_option(16, tries); c.set_option(17, fan)
+        c.set_option(OPT_PROPOSE_VARIANT, 4); c.set_option(OPT_BLOCKED, rounds); c.set_option(OPT_BLK_MFMA, 1); c.set_option(OPT_BLK_TRIES, tries); c.set_option(OPT_BLK_FAN, fan)
         up, mu_, mup = c.empty(d, n), c.empty(n), c.empty(n)
         state = c.zeros(10)
         c.propose(kernel, soa(u, dev), None, modes, st, ft, seed, tick, item0, up, mu_, mup, ctl=state)
         got[fan] = (aos(up), mu_.cpu().numpy(), mup.cpu().numpy())
-    c.set_option(0, 0); c.set_option(4, 0); c.set_option(16, 0); c.set_option(17, 1)
+    c.set_option(OPT_PROPOSE_VARIANT, 0); c.set_option(OPT_BLOCKED, 0); c.set_option(OPT_BLK_TRIES, 0); c.set_option(OPT_BLK_FAN, 1)
     # (to rounding, not bit for bit: WHICH kernel evaluates a particle's winning attempt -- a matrix-core round or the screened
     # kernel's FP64 chain -- depends on the round that settles it, and the two sum a row in different orders)
     np.testing.assert_allclose(got[1][0], got[0][0], rtol=1e-12, atol=1e-15)
@@ -934,10 +937,10 @@ def test_blocked_rounds_with_several_modes_vs_oracle_and_multilane(dev, kernel, 
     got = {}
     for variant in (4, 3, 40):                           # 40: variant 4 with the list rounds NOT fanned out (TPH_OPT_BLK_FAN = 0)
         c = ctx_for(d)
-        c.set_option(0, 4 if variant == 40 else variant)
-        c.set_option(4, rounds if variant != 3 else 0)
-        c.set_option(16, 1 if d in (19, 50) else 2)      # TPH_OPT_BLK_TRIES
-        c.set_option(17, 0 if variant == 40 else 1)      # TPH_OPT_BLK_FAN (per mode: width and next attempt from the mode's own list)
+        c.set_option(OPT_PROPOSE_VARIANT, 4 if variant == 40 else variant)
+        c.set_option(OPT_BLOCKED, rounds if variant != 3 else 0)
+        c.set_option(OPT_BLK_TRIES, 1 if d in (19, 50) else 2)      # TPH_OPT_BLK_TRIES
+        c.set_option(OPT_BLK_FAN, 0 if variant == 40 else 1)      # TPH_OPT_BLK_FAN (per mode: width and next attempt from the mode's own list)
         up, mu_, mup = c.empty(d, n), c.empty(n), c.empty(n)
         state = c.zeros(10)
         c.propose(kernel, soa(u, dev), at, modes, st, ft, seed, tick, item0, up, mu_, mup, ctl=state)
@@ -975,8 +978,8 @@ def test_blocked_kernel_deferred_update_and_step_control(dev, kernel, mfma):
     st = torch.from_numpy(np.array([0.5 * (2.38 / np.sqrt(d) if kernel == "rwm" else 1.0)])).to(dev)
     u0 = np.clip(means[0] + 0.05 * rs.randn(n, d), 0.002, 0.998)
     c = ctx_for(d)
-    c.set_option(0, 4)
-    c.set_option(15, mfma)
+    c.set_option(OPT_PROPOSE_VARIANT, 4)
+    c.set_option(OPT_BLK_MFMA, mfma)
 
     def like(up):
         x = 20 * up - 10
@@ -1040,9 +1043,9 @@ def test_stage_machine_proposal_kernel_vs_oracle_and_multilane(dev, kernel, bc, 
     got = {}
     for variant in (5, 3):
         c = HipContext(d, device=0)
-        c.set_option(0, variant)
-        c.set_option(10, lanes)            # TPH_OPT_SM_LANES
-        c.set_option(11, zl)               # TPH_OPT_SM_THRESHOLD
+        c.set_option(OPT_PROPOSE_VARIANT, variant)
+        c.set_option(OPT_SM_LANES, lanes)            # TPH_OPT_SM_LANES
+        c.set_option(OPT_SM_THRESHOLD, zl)               # TPH_OPT_SM_THRESHOLD
         up, mu_, mup = c.empty(d, n), c.empty(n), c.empty(n)
         state = c.zeros(10)
         c.propose(kernel, soa(u, dev), None, modes, st, ft, seed, tick, item0, up, mu_, mup, ctl=state)
@@ -1076,7 +1079,7 @@ def test_stage_machine_redraw_cap_proposes_the_current_point(dev, kernel):
     u = rs.rand(n, d)
     st = torch.from_numpy(np.array([0.99 if kernel == "tpcn" else 30.0])).to(dev)
     c = HipContext(d, device=0)
-    c.set_option(0, 5)
+    c.set_option(OPT_PROPOSE_VARIANT, 5)
     up, mu_, mup = c.empty(d, n), c.empty(n), c.empty(n)
     state = c.zeros(10)
     c.propose(kernel, soa(u, dev), None, modes, st, None, 5, 3, 0, up, mu_, mup, ctl=state)
@@ -1105,7 +1108,7 @@ def test_stage_machine_kernel_deferred_update_and_step_control(dev, kernel):
     st = torch.from_numpy(np.array([0.8 * 2.38 / np.sqrt(d)])).to(dev)
     u0 = rs.rand(n, d)
     c = ctx_for(d)
-    c.set_option(0, 5)
+    c.set_option(OPT_PROPOSE_VARIANT, 5)
 
     def like(up):
         x = 20 * up - 10
@@ -1137,7 +1140,7 @@ def test_stage_machine_kernel_deferred_update_and_step_control(dev, kernel):
             assert torch.equal(x, y)
     assert torch.equal(ua, ub)
     assert 0 < float(ta[0][2][0]) < n
-    c.set_option(0, 0)
+    c.set_option(OPT_PROPOSE_VARIANT, 0)
 
 
 @pytest.mark.parametrize("d", [3, 10, 50])
@@ -1269,9 +1272,9 @@ def test_stage_machine_odd_sizes_vs_multilane(dev, kernel, d):
         got = {}
         for variant in (5, 3):
             c = HipContext(d, device=0)
-            c.set_option(0, variant)
-            c.set_option(10, lanes)
-            c.set_option(11, zl)
+            c.set_option(OPT_PROPOSE_VARIANT, variant)
+            c.set_option(OPT_SM_LANES, lanes)
+            c.set_option(OPT_SM_THRESHOLD, zl)
             up, mu_, mup = c.empty(d, n), c.empty(n), c.empty(n)
             c.propose(kernel, soa(u, dev), None, modes, st, None, 4242, 9, 123456789, up, mu_, mup)
             got[variant] = (aos(up), mup.cpu().numpy())
@@ -1304,16 +1307,16 @@ def test_blocked_rounds_with_panels_staged_in_lds_equal_the_streamed_ones(dev, k
     got = {}
     for stage in (0, 1):
         c = ctx_for(d)
-        c.set_option(0, 4)                 # blocked path
-        c.set_option(4, rounds)
-        c.set_option(15, 1)                # matrix cores
-        c.set_option(16, 1)                # one try per round (the staged kernel's case)
-        c.set_option(20, stage)            # TPH_OPT_BLK_STAGE
+        c.set_option(OPT_PROPOSE_VARIANT, 4)                 # blocked path
+        c.set_option(OPT_BLOCKED, rounds)
+        c.set_option(OPT_BLK_MFMA, 1)                # matrix cores
+        c.set_option(OPT_BLK_TRIES, 1)                # one try per round (the staged kernel's case)
+        c.set_option(OPT_BLK_STAGE, stage)            # TPH_OPT_BLK_STAGE
         up, mu_, mup = c.empty(d, n), c.empty(n), c.empty(n)
         state = c.zeros(10)
         c.propose(kernel, soa(u, dev), None, modes, st, ft, seed, tick, item0, up, mu_, mup, ctl=state)
         got[stage] = (aos(up), mu_.cpu().numpy(), mup.cpu().numpy(), state.cpu().numpy())
-        c.set_option(20, 0); c.set_option(4, 0); c.set_option(16, 0); c.set_option(0, 0)
+        c.set_option(OPT_BLK_STAGE, 0); c.set_option(OPT_BLOCKED, 0); c.set_option(OPT_BLK_TRIES, 0); c.set_option(OPT_PROPOSE_VARIANT, 0)
     for a, b in zip(got[0], got[1]):
         np.testing.assert_array_equal(a, b)
     want_up = omc.propose(kernel, u, np.zeros(n, dtype=np.int32), means, chol, inv, dof, sigmas, flags, seed, tick, item0)[0]

@@ -28,9 +28,10 @@ torch = pytest.importorskip("torch")
 
 from tests import propose_reg_cases as pc  # noqa: E402
 from tests.test_kernels_gpu import _Modes, aos, soa  # noqa: E402
+from tempest_amd.device import OPT_PROPOSE_VARIANT as OPT_VARIANT  # noqa: E402
+from tempest_amd.device import OPT_REDRAW_LANES  # noqa: E402
 
 GUARD, SENT = 128, 1e300
-OPT_VARIANT, OPT_REDRAW_LANES = 0, 2          # TPH_OPT_PROPOSE_VARIANT, TPH_OPT_REDRAW_LANES
 SLICE = 2048                                  # rows of one oracle comparison inside a large launch
 
 

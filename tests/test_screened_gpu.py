@@ -18,8 +18,8 @@ from oracle import mcmc as omc  # noqa: E402
 from oracle import ps  # noqa: E402
 
 from tests.test_kernels_gpu import _Modes, aos, ctx_for, dev, soa  # noqa: E402,F401
-
-OPT_VARIANT, OPT_SM_LANES, OPT_MF_LANES, OPT_MF_AUDIT = 0, 10, 13, 14
+from tempest_amd.device import OPT_PROPOSE_VARIANT as OPT_VARIANT  # noqa: E402
+from tempest_amd.device import OPT_BLOCKED, OPT_FORMS_MFMA, OPT_MF_AUDIT, OPT_MF_LANES, OPT_SM_LANES  # noqa: E402
 
 
 def _ensemble(d, n, seed, spread=0.29, easy=40):
@@ -322,8 +322,8 @@ def test_forms_behind_the_screened_batches_on_the_matrix_cores(dev, bc, d):
         for mf in (0, 1):
             c = HipContext(d, device=0)
             c.set_option(OPT_VARIANT, variant)
-            c.set_option(4, rounds)
-            c.set_option(22, mf)                      # TPH_OPT_FORMS_MFMA
+            c.set_option(OPT_BLOCKED, rounds)
+            c.set_option(OPT_FORMS_MFMA, mf)                      # TPH_OPT_FORMS_MFMA
             up, mu_, mup = c.empty(d, n), c.empty(n), c.empty(n)
             state = c.zeros(10)
             c.propose("tpcn", soa(u, dev), None, modes, st, ft, seed, tick, item0, up, mu_, mup, ctl=state)

@@ -50,6 +50,8 @@ def main():
     a = ap.parse_args()
     import torch
     from tempest_amd import _lib
+    from tempest_amd.device import (OPT_BLK_MFMA, OPT_BLOCKED, OPT_MF_AUDIT, OPT_MF_LANES, OPT_ML_UNSTAGED, OPT_MODES_EPOCH,
+                                    OPT_PROPOSE_VARIANT, OPT_REDRAW_LANES, OPT_SCREEN, OPT_SM_LANES, OPT_SM_THRESHOLD)
     lib = _lib.load(a.lib) if not (a.legacy or a.older) else C.CDLL(a.lib)
     if a.older:                           # an earlier round's library with today's tph_propose signature: bind what it exports
         for name, (res, args) in _lib.SIGNATURES.items():
@@ -76,27 +78,27 @@ def main():
     stream = torch.cuda.current_stream(dev).cuda_stream
     assert lib.tph_ctx_create(0, d, 0, C.c_void_p(stream), C.byref(ctx)) == 0
     if a.variant:
-        lib.tph_set_option(ctx, 0, a.variant)
+        lib.tph_set_option(ctx, OPT_PROPOSE_VARIANT, a.variant)
     if a.wpe:
-        lib.tph_set_option(ctx, 2, a.wpe)
+        lib.tph_set_option(ctx, OPT_REDRAW_LANES, a.wpe)
     if a.unstaged:
-        lib.tph_set_option(ctx, 3, 1)
+        lib.tph_set_option(ctx, OPT_ML_UNSTAGED, 1)
     if a.lanes:
-        lib.tph_set_option(ctx, 10, a.lanes)
+        lib.tph_set_option(ctx, OPT_SM_LANES, a.lanes)
     if a.thr:
-        lib.tph_set_option(ctx, 11, a.thr)
+        lib.tph_set_option(ctx, OPT_SM_THRESHOLD, a.thr)
     if a.rounds:
-        lib.tph_set_option(ctx, 4, a.rounds)
+        lib.tph_set_option(ctx, OPT_BLOCKED, a.rounds)
     if a.mflanes:
-        lib.tph_set_option(ctx, 13, a.mflanes)
+        lib.tph_set_option(ctx, OPT_MF_LANES, a.mflanes)
     if a.audit:
-        lib.tph_set_option(ctx, 14, 1)
+        lib.tph_set_option(ctx, OPT_MF_AUDIT, 1)
     if a.noscreen:
-        lib.tph_set_option(ctx, 12, 0)
+        lib.tph_set_option(ctx, OPT_SCREEN, 0)
     if a.nomfma:
-        lib.tph_set_option(ctx, 15, 0)
+        lib.tph_set_option(ctx, OPT_BLK_MFMA, 0)
     if a.epoch:
-        lib.tph_set_option(ctx, 5, a.epoch)
+        lib.tph_set_option(ctx, OPT_MODES_EPOCH, a.epoch)
     kid = {"tpcn": 0, "rwm": 1}[a.kernel]
     rs = np.random.RandomState(0)
     for scen in a.scen.split(","):

@@ -29,6 +29,7 @@ def main():
     a = ap.parse_args()
     import torch
     from tempest_amd import _lib
+    from tempest_amd.device import OPT_BLK_TRIES, OPT_BLOCKED, OPT_MF_LANES, OPT_MODES_EPOCH, OPT_PROPOSE_VARIANT
     lib = _lib.load()
     dev = torch.device("cuda", 0)
     kid = {"tpcn": 0, "rwm": 1}[a.kernel]
@@ -52,7 +53,7 @@ def main():
             mu_, mup = torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.float64, device=dev)
             ctl = torch.zeros(10, dtype=torch.float64, device=dev)
             epoch += 1
-            lib.tph_set_option(ctx, 5, epoch)          # TPH_OPT_MODES_EPOCH: the packed copies are rebuilt once per ensemble, as in a run
+            lib.tph_set_option(ctx, OPT_MODES_EPOCH, epoch)          # the packed copies are rebuilt once per ensemble, as in a run
 
             def launch(tick, carry=True):
                 rc = lib.tph_propose(ctx, kid, p(u), None, n, n, 1, p(means), p(chol), p(winv), p(dof), p(sig), None, 12345, tick, 0,
@@ -60,10 +61,10 @@ def main():
                 assert rc == 0, lib.tph_last_error()
 
             def timed(variant, rounds=0, lanes=0, tries=1):
-                lib.tph_set_option(ctx, 0, variant)
-                lib.tph_set_option(ctx, 4, rounds)
-                lib.tph_set_option(ctx, 13, lanes)
-                lib.tph_set_option(ctx, 16, tries)
+                lib.tph_set_option(ctx, OPT_PROPOSE_VARIANT, variant)
+                lib.tph_set_option(ctx, OPT_BLOCKED, rounds)
+                lib.tph_set_option(ctx, OPT_MF_LANES, lanes)
+                lib.tph_set_option(ctx, OPT_BLK_TRIES, tries)
                 ctl[0] = 0.0
                 launch(1, False)
                 ctl[0] = 1.0

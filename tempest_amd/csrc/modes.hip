@@ -631,7 +631,8 @@ __global__ void __launch_bounds__(256) k_wcov(const double* __restrict__ hu, int
 // n_dim >= 16: the same staged tile, but a thread owns a 4 x 4 BLOCK of the lower triangle over a slice of the tile's rows:
 // per row 1 + 4 + 4 LDS reads feed 16 FMAs (the pair-per-thread form above reads w, x_a, x_b for every single FMA and is
 // LDS-bound: 0.5 TFLOP/s at d = 32).  Items = (block pair, row slice); slices exist only while there are fewer block pairs
-// than threads (d <= 64) and meet in a fixed order through an LDS copy of the triangle (no float atomics).
+// than half the threads (d <= 60: 16 slices up to d = 20, 8 to 28, 4 to 40, 2 to 60; d = 61 has 136 block pairs and none) and
+// meet in a fixed order through an LDS copy of the triangle (no float atomics).
 constexpr int COV_TB = 4;
 __host__ __device__ inline int cov_tile_slices(int d) {
   const int nbk = (d + COV_TB - 1) / COV_TB, pairs = nbk * (nbk + 1) / 2;

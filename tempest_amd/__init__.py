@@ -4,7 +4,7 @@ __version__ = "0.1.0"
 
 from .sampler import Sampler
 
-__all__ = ["Sampler", "HipCallbacks", "trace_callbacks", "Noise", "Prior", "priors"]
+__all__ = ["Sampler", "HipCallbacks", "trace_callbacks", "Noise", "Prior", "priors", "compare_pointwise"]
 
 
 def __getattr__(name):          # lazy: importing the package must not need hipcc or a GPU
@@ -20,6 +20,9 @@ def __getattr__(name):          # lazy: importing the package must not need hipc
     if name == "Prior":         # independent priors column by column: a traceable prior_transform, its HIP text, its log density
         from .priors import Prior
         return Prior
+    if name == "compare_pointwise":     # two models on the same observations by a pointwise value of Sampler.pointwise()
+        from .hipcallbacks import compare_pointwise
+        return compare_pointwise
     if name == "priors":
         import importlib
         return importlib.import_module(".priors", __name__)

@@ -400,9 +400,10 @@ class SamplerCore:
             raise TempestHipError(f"Sampler.{what}: the likelihood is no HipCallbacks source {needs}")
         return owner
 
-    def _weighted_rows(self, what, unbuilt, trim_importance_weights, ess_trim, bins_trim, owner=None):
+    def _weighted_rows(self, what, unbuilt, trim_importance_weights, ess_trim, bins_trim, owner=None, with_sel=False):
         """(x_dev, w_sel): the rows and weights compute_posterior returns (same selection and row order), left on the device -- for
-        `owner`, a HipCallbacks object, on its device.  One shard only: Sampler.`what` needs `unbuilt` to fold the ranks' parts."""
+        `owner`, a HipCallbacks object, on its device; with_sel: (x_dev, w_sel, sel), sel their device indices into the history (None:
+        its first rows).  One shard only: Sampler.`what` needs `unbuilt` to fold the ranks' parts."""
         st = self.state
         if st.comm is not None and st.comm.active:
             raise NotImplementedError(f"Sampler.{what} is not available on a sharded run yet: every rank holds a part of the rows, and "
@@ -415,7 +416,7 @@ class SamplerCore:
         w_dev = ctx.weights(1.0, m, s1)
         sel, m_sel, wdiv = self._select_rows(w_dev, trim_importance_weights, ess_trim, bins_trim)
         x_dev, _, w_sel = ctx.posterior_rows(sel, m_sel, w=w_dev, wdiv=wdiv)
-        return x_dev, w_sel
+        return (x_dev, w_sel, sel) if with_sel else (x_dev, w_sel)
 
     def compute_predictive(self, quantiles=(0.025, 0.5, 0.975), trim_importance_weights=True, ess_trim=0.99, bins_trim=1000):
         """Posterior predictive mean, variance and quantiles of the HipCallbacks source's predict(x, r) over the rows and weights
@@ -435,15 +436,36 @@ class SamplerCore:
                                            trim_importance_weights, ess_trim, bins_trim, owner)
         return owner.replicated(x_dev, w_sel, quantiles, seed=self.rng.seed if seed is None else seed)
 
-    def compute_pointwise(self, trim_importance_weights=True, ess_trim=0.99, bins_trim=1000):
+    _psis_rows = None          # the equally weighted rows the last compute_pointwise handed to psis_loo (tests)
+
+    def compute_pointwise(self, trim_importance_weights=True, ess_trim=0.99, bins_trim=1000, psis_draws=None, seed=None):
         """Pointwise log predictive densities, WAIC and importance-sampling LOO of a pointwise-enabled HipCallbacks source over the
         rows and weights compute_posterior returns (same selection, on the device): the rows are gathered and reduced there, only
-        the (n_terms,) results reach the host."""
+        the (n_terms,) results reach the host.  A source built with pointwise="psis" adds the Pareto-smoothed values of
+        HipCallbacks.psis_loo over psis_draws (None: as many as there are weighted rows) equally weighted rows, drawn from the
+        weighted ones by systematic resampling on the device at the offset `seed` (None: the run's seed) gives."""
         owner = self._hip_owner("pointwise", "pointwise_enabled",
                                 "built with pointwise=True (give it, with a source that defines log_likelihood_term)")
-        x_dev, w_sel = self._weighted_rows("pointwise", "folding per-rank maxima, minima and partial sums is not built",
-                                           trim_importance_weights, ess_trim, bins_trim, owner)
-        return owner.pointwise(x_dev, w_sel)
+        x_dev, w_sel, sel = self._weighted_rows("pointwise", "folding per-rank maxima, minima and partial sums is not built",
+                                                trim_importance_weights, ess_trim, bins_trim, owner, with_sel=True)
+        res = owner.pointwise(x_dev, w_sel)
+        if owner.psis_enabled:
+            from .hipcallbacks import PSIS_KEYS
+            from .tools import SQRTEPS
+            n_draws = x_dev.shape[0] if psis_draws is None else psis_draws
+            if isinstance(n_draws, bool) or not isinstance(n_draws, (int, np.integer)) or int(n_draws) <= 0:
+                raise ValueError(f"Sampler.pointwise: psis_draws must be a positive int, got {psis_draws!r}")
+            ctx = self.state.ctx
+            cdf = ctx.cdf(w_sel)
+            tot = float(cdf[-1].item())
+            u0 = float(np.random.default_rng(self.rng.seed if seed is None else seed).random())
+            pick = ctx.resample_systematic(cdf, int(n_draws), u0, renorm=tot if abs(tot - 1.0) > SQRTEPS else 1.0)
+            rows, _, _ = ctx.posterior_rows(pick if sel is None else ctx.index_compose(sel, pick), int(n_draws))
+            self._psis_rows = rows
+            ps = owner.psis_loo(rows)
+            res.update((k, ps[k]) for k in PSIS_KEYS)
+            res["totals"].update(ps["totals"], p_psis=res["totals"]["lppd"] - ps["totals"]["elpd_psis"], k_threshold=ps["k_threshold"])
+        return res
 
     def compute_marginals(self, bins=64, range=None, quantiles=(0.025, 0.16, 0.5, 0.84, 0.975), pairs=None, bins_2d=32, derived=True,
                           trim_importance_weights=True, ess_trim=0.99, bins_trim=1000):

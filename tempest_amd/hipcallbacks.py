@@ -27,6 +27,7 @@ import ctypes as C
 from collections import namedtuple
 import hashlib
 import keyword
+import math
 import os
 import re
 import shutil
@@ -113,6 +114,14 @@ POINTWISE_SCRATCH_WORDS = 1 << 23  # 64 MiB of batch scratch at most: more indic
 # r in SUM_LAYOUT; tiles by predict_tiles.
 REPLICATE_TAGS = (TAG_REP_NORMAL, TAG_REP_UNIFORM)
 POINTWISE_KEYS = ("lppd", "mean", "p_waic", "elpd_waic", "elpd_loo", "ess_loo")      # the rows of tphu_pointwise's output
+# psis_loo(): Pareto-smoothed importance-sampling LOO over equally weighted rows.  The tail of an observation -- its
+# ceil(min(0.2 n, 3 sqrt(n))) largest ratios, at most PSIS_MAX_TAIL (TPHU_PSIS_MAXTAIL: what a workgroup of the fit sorts in LDS; n up to
+# 1 864 135 rows is not clamped), none below PSIS_MIN_TAIL -- is sorted and refitted by one workgroup; body sums run in PREDICT_SUM_LAYOUT,
+# tiles by pointwise_tiles, the select's slab by predict_tiles.  Neither decides a bit of the result.
+PSIS_MAX_TAIL = 4096
+PSIS_MIN_TAIL = 5
+PSIS_SCRATCH_WORDS = 1 << 23       # 64 MiB of batch scratch at most: more indices than fit go through in batches
+PSIS_KEYS = ("pareto_k", "elpd_psis", "ess_psis")                                     # the rows of tphu_psis's output
 
 
 def prefer_split(n: int, n_terms: int) -> bool:
@@ -246,6 +255,54 @@ def pointwise_scratch_words(n: int, n_terms: int) -> int:
     return 1 + n_blocks + per_r * min(n_terms, max(1, POINTWISE_SCRATCH_WORDS // per_r))
 
 
+def psis_tail_len(n: int) -> int:
+    """The tail length M of psis_loo() over n rows: ceil(min(0.2 n, 3 sqrt(n))), at most PSIS_MAX_TAIL; below PSIS_MIN_TAIL nothing is
+    smoothed."""
+    return min(int(math.ceil(min(0.2 * n, 3.0 * math.sqrt(n)))), PSIS_MAX_TAIL)
+
+
+def psis_k_threshold(n: int) -> float:
+    """The pareto_k above which an estimate from n rows is not to be trusted: min(1 - 1 / log10(n), 0.7)."""
+    return min(1.0 - 1.0 / math.log10(n), 0.7) if n > 1 else float("-inf")
+
+
+def psis_scratch_words(n: int, n_terms: int) -> int:
+    """8-byte words of scratch tphu_psis gets for this call: W and the block sums of w, and for a batch of indices the bucket totals,
+    prefix, target, NaN flag, slot counter, cut, mean and the two shifts (264 words), three arrays of block values and the tail's M
+    slots -- all n_terms indices, or as many as PSIS_SCRATCH_WORDS hold."""
+    n_blocks = _row_blocks(n)
+    tail = psis_tail_len(n)
+    per_r = 3 * n_blocks + 264 + (tail if tail >= PSIS_MIN_TAIL else 0)
+    return 1 + n_blocks + per_r * min(n_terms, max(1, PSIS_SCRATCH_WORDS // per_r))
+
+
+def compare_pointwise(a, b, key="elpd_loo"):
+    """Two models on the SAME observations by a pointwise value (`key` of what pointwise() returned for each, or two arrays):
+    {"diff": sum (a - b), "se": sqrt(n x the population variance of a - b), "n"}.  Unequal lengths are refused."""
+    va, vb = (np.asarray(v[key] if isinstance(v, dict) else v, dtype=np.float64) for v in (a, b))
+    if va.ndim != 1 or va.shape != vb.shape or va.size == 0:
+        raise ValueError(f"compare_pointwise: expected two (n,) arrays of the same observations, got {va.shape} and {vb.shape}")
+    with np.errstate(invalid="ignore", over="ignore"):
+        d = va - vb
+        return {"diff": _total(d), "se": float(np.sqrt(d.size * np.var(d))), "n": int(d.size)}
+
+
+def _total(v) -> float:
+    """The sum of pointwise values: exact (math.fsum); +inf beside -inf among them: what a plain sum makes of them."""
+    try:
+        return math.fsum(v)
+    except (ValueError, OverflowError):
+        with np.errstate(invalid="ignore", over="ignore"):
+            return float(np.sum(v))
+
+
+def psis_totals(res, k_threshold) -> dict:
+    """The totals of psis_loo()'s pointwise arrays: elpd_psis, elpd_psis_se, n_high_k (a NaN or infinite pareto_k counts)."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        return {"elpd_psis": _total(res["elpd_psis"]), "elpd_psis_se": float(np.sqrt(len(res["elpd_psis"]) * np.var(res["elpd_psis"]))),
+                "n_high_k": int(np.sum(~(res["pareto_k"] <= k_threshold)))}
+
+
 def _quantiles(quantiles, what):
     """The quantile levels of predictive() / replicated() as a checked float64 array."""
     qs = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
@@ -335,14 +392,16 @@ _PARTS = (
           "tphu_predict_layout", _PREDICT_LAYOUT, "predict() sum layout or tile limits do"),
     _Part("pointwise", "//@W", "-DTPHU_POINTWISE", "|pointwise", "tphu_pointwise",
           "tphu_pointwise_layout", PREDICT_SUM_LAYOUT + (POINTWISE_MAX_TILE,), "pointwise sum layout or tile limit does"),
+    _Part("psis", "//@K", "-DTPHU_PSIS", "|psis", "tphu_psis",
+          "tphu_psis_layout", PREDICT_SUM_LAYOUT + (POINTWISE_MAX_TILE, PREDICT_TABLES, PSIS_MAX_TAIL), "psis sum layout, tile limits or tail limit do"),
     _Part("replicate", "//@Y", "-DTPHU_REPLICATE", "|replicate", "tphu_replicated",
           "tphu_replicate_layout", _PREDICT_LAYOUT + SUM_LAYOUT + REPLICATE_TAGS, "replicate() sum layouts, tile limits or RNG tags do"),
     _Part("discrepancy", None, "-DTPHU_DISCREPANCY", "|discrepancy"),
 )
 
 
-class _Parts(namedtuple("_Parts", "tables term n_derived predict pointwise replicate discrepancy traced",
-                        defaults=(None, False, 0, False, False, False, False, False))):
+class _Parts(namedtuple("_Parts", "tables term n_derived predict pointwise replicate discrepancy traced psis",
+                        defaults=(None, False, 0, False, False, False, False, False, False))):
     """What a plugin has beside the two callbacks of x: the record every difference between two plugins derives from -- the template
     lines kept, the -D list, the words of the key, the entry points bound and the layouts checked.  tables None: callbacks of x alone
     (the template as it always was, byte for byte); ((name, rank), ...): the callbacks take `const tphu_data& D` and every kernel and
@@ -350,16 +409,21 @@ class _Parts(namedtuple("_Parts", "tables term n_derived predict pointwise repli
     derived(x, out) (k_user_derived / tphu_derived); predict: predict(x, r) (the k_user_predict_* kernels / tphu_predictive);
     pointwise (term form only): the k_user_pw_* kernels / tphu_pointwise; replicate: replicate(x, r, g) (tphu_noise, the k_user_rep_*
     kernels / tphu_replicated), with discrepancy where the source also gives discrepancy(); traced: the source calls the helpers of
-    tempest_amd.trace (tphu_tr_max / tphu_tr_min)."""
+    tempest_amd.trace (tphu_tr_max / tphu_tr_min); psis (with pointwise, which then was given as "psis"): the k_user_psis_* kernels /
+    tphu_psis."""
     __slots__ = ()
 
     @classmethod
     def of(cls, source, tables=None, term=False, n_derived=0, predict=False, pointwise=False, replicate=False, discrepancy=False):
         return cls(() if term and tables is None else tables, bool(term), max(0, int(n_derived)), bool(predict), bool(pointwise),
-                   bool(replicate), bool(replicate and discrepancy), re.search(r"\btphu_tr_(max|min)\s*\(", source) is not None)
+                   bool(replicate), bool(replicate and discrepancy), re.search(r"\btphu_tr_(max|min)\s*\(", source) is not None,
+                   isinstance(pointwise, str) and pointwise == "psis")
 
     def build_args(self) -> dict:          # the keyword arguments of build_plugin that give this record back
-        return {k: v for k, v in self._asdict().items() if k != "traced"}
+        args = {k: v for k, v in self._asdict().items() if k not in ("traced", "psis")}
+        if self.psis:                      # the level travels in `pointwise`
+            args["pointwise"] = "psis"
+        return args
 
     def present(self):
         return [part for part in _PARTS if getattr(self, part.name)]
@@ -367,10 +431,10 @@ class _Parts(namedtuple("_Parts", "tables term n_derived predict pointwise repli
     def text(self, source: str) -> str:
         """The translation unit for `source`."""
         # lines of one part only are dropped whole without it; //@D: the data form; //@Q: what predict, pointwise and replicate share --
-        # the layout constants, the row loads, the sum of the weights; //@S: what predict and replicate share -- the fold of the block
+        # the layout constants, the row loads, the sum of the weights; //@S: what predict, replicate and psis share -- the fold of the block
         # sums, the select's key and its narrowing kernel; //@R: the helpers a traced source calls
         rows = self.predict or self.pointwise or self.replicate
-        keep = {"//@D": self.tables is not None, "//@S": self.predict or self.replicate, "//@Q": rows, "//@R": self.traced}
+        keep = {"//@D": self.tables is not None, "//@S": self.predict or self.replicate or self.psis, "//@Q": rows, "//@R": self.traced}
         keep.update((part.mark, bool(getattr(self, part.name))) for part in _PARTS if part.mark)
         out = []
         for line in _TEMPLATE.read_text().split("\n"):
@@ -502,9 +566,10 @@ class HipCallbacks:
     # tile > 0 pins the indices per workgroup of predictive() (1 .. 64); (tile, slab) also the rows per workgroup of its select
     n_predict, predict_tile, predict_sum_layout = 0, 0, PREDICT_SUM_LAYOUT
     pointwise_enabled, pointwise_tile = False, 0      # tile > 0 pins the indices per workgroup of pointwise() (1 .. 64)
+    psis_enabled, psis_scratch_cap = False, 0         # cap > 0 pins the words of batch scratch psis_loo() asks for (tests: several batches)
     n_replicate, observed, has_discrepancy = 0, None, False
     run_groups = 0                         # > 0 limits the workgroups of tphu_run's launch (tests: several tiles per workgroup)
-    _device = _dev_tables = _dstruct = _struct_type = _bsum = _pscratch = _wscratch = _yscratch = None
+    _device = _dev_tables = _dstruct = _struct_type = _bsum = _pscratch = _wscratch = _yscratch = _kscratch = None
 
     def __init__(self, source: str, n_dim: int, fused: bool = True, verbose: bool = False, whole_step: bool = True,
                  persistent: bool = False, data=None, n_terms=None, n_derived=None, n_predict=None, *,
@@ -521,7 +586,7 @@ class HipCallbacks:
             raise ValueError("HipCallbacks: log_likelihood_term needs n_terms= (an int, or the name of a data entry)")
         if n_terms is not None and not has_term:
             raise ValueError("HipCallbacks: n_terms= goes with a source that defines log_likelihood_term")
-        if not isinstance(pointwise, (bool, np.bool_)):
+        if not isinstance(pointwise, (bool, np.bool_)) and not (isinstance(pointwise, str) and pointwise == "psis"):
             raise ValueError(f"HipCallbacks: pointwise must be True or False, got {pointwise!r}")
         if pointwise and not has_term:
             raise ValueError("HipCallbacks: pointwise=True goes with a source that defines log_likelihood_term (and n_terms=)")
@@ -547,6 +612,7 @@ class HipCallbacks:
         self.persistent = bool(persistent) if env is None else env != "0"
         self.parts = _Parts.of(source, tables, has_term, self.n_derived, self.n_predict, pointwise, self.n_replicate, self.has_discrepancy)
         self.tables, self.term, self.pointwise_enabled = self.parts.tables, self.parts.term, self.parts.pointwise
+        self.psis_enabled = self.parts.psis
         self.path = build_plugin(source, n_dim, verbose, **self.parts.build_args())
         import torch  # noqa: F401  (its HIP runtime must be the one in the process, as for libtempest_hip)
         self.lib = C.CDLL(str(self.path))
@@ -845,7 +911,6 @@ class HipCallbacks:
         elpd_waic, p_waic, lppd, elpd_loo, p_loo = lppd - elpd_loo, and elpd_waic_se, elpd_loo_se = sqrt(n_terms x the population
         variance of the pointwise values).  Nothing of size n x n_terms is formed; only the (6, n_terms) results come to the host
         (DESIGN.md section 11).  The scratch is one buffer kept on this object, as for predictive()."""
-        import math
         import torch
         if not self.pointwise_enabled:
             raise TempestHipError("HipCallbacks.pointwise: the object was built without pointwise=True (give it, with a source that defines "
@@ -859,19 +924,46 @@ class HipCallbacks:
         self._check(self.lib.tphu_pointwise(self._stream(x), x.data_ptr(), w.data_ptr(), n, R, out.data_ptr(), scratch.data_ptr(),
                                             words, tile, *self._data()), "tphu_pointwise")
         res = {k: v.copy() for k, v in zip(POINTWISE_KEYS, out.cpu().numpy())}
-
-        def total(v):
-            try:
-                return math.fsum(v)
-            except (ValueError, OverflowError):      # +inf beside -inf among the pointwise values: what a plain sum makes of them
-                with np.errstate(invalid="ignore", over="ignore"):
-                    return float(np.sum(v))
-        tot = {k: total(res[k]) for k in ("elpd_waic", "p_waic", "lppd", "elpd_loo")}
+        tot = {k: _total(res[k]) for k in ("elpd_waic", "p_waic", "lppd", "elpd_loo")}
         tot["p_loo"] = tot["lppd"] - tot["elpd_loo"]
         with np.errstate(invalid="ignore", over="ignore"):
             for k in ("elpd_waic", "elpd_loo"):
                 tot[k + "_se"] = float(np.sqrt(R * np.var(res[k])))
         res.update(n_rows=n, ess=s1 * s1 / s2, totals=tot)
+        return res
+
+    def psis_loo(self, x):
+        """Pareto-smoothed importance-sampling leave-one-out (Vehtari, Gelman & Gabry) of a term-form source built with
+        pointwise="psis", over the (n, n_dim) EQUALLY weighted rows x (torch-ROCm tensor or NumPy array).  Per observation r, with a_i =
+        log_likelihood_term(x_i, r, D) and the log ratios l_i = min a - a_i: the M = "tail_len" largest ratios are refitted by a
+        generalised Pareto distribution (Zhang & Stephens, as loo::gpdfit) and replaced by its order statistics.  A dict of NumPy arrays
+        (n_terms,): "pareto_k", the fitted shape -- above "k_threshold" = min(1 - 1 / log10(n), 0.7) the estimate is not to be trusted;
+        +inf where nothing was smoothed (M < 5, a degenerate tail) and "elpd_psis" is the plain importance-sampling value --, "elpd_psis",
+        "ess_psis" = 1 / sum v^2 over the normalised smoothed ratios v; and "tail_len", "n_rows", "k_threshold", "totals": elpd_psis
+        (math.fsum), elpd_psis_se = sqrt(n_terms x the population variance), n_high_k = how many pareto_k exceed the threshold (a NaN
+        counts).  A NaN term makes all three NaN; min a = -inf or +inf is elpd_psis, with pareto_k and ess_psis NaN.  Nothing of size n x
+        n_terms is formed; no tile, batch or launch shape changes a bit.  The scratch is one buffer kept on this
+        object, as for predictive()."""
+        import torch
+        if not self.psis_enabled:
+            raise TempestHipError('HipCallbacks.psis_loo: the object was built without pointwise="psis" (give it, with a source that '
+                                  "defines log_likelihood_term)")
+        x = self._on_device(x)
+        if x.dim() != 2 or x.shape[1] != self.n_dim or x.shape[0] == 0:
+            raise ValueError(f"psis_loo: expected (n, {self.n_dim}) points with n > 0, got {tuple(x.shape)}")
+        self._on_table_device(x, "psis_loo")
+        n, R = x.shape[0], self.n_terms
+        tail = psis_tail_len(n)
+        tile = int(self.pointwise_tile) or pointwise_tiles(n, R)
+        slab = predict_tiles(n, R, 1)[1]
+        words = int(self.psis_scratch_cap) or psis_scratch_words(n, R)
+        scratch = self._kept_scratch("_kscratch", words, x.device)
+        ones = torch.ones(n, dtype=torch.float64, device=x.device)
+        out = torch.empty((len(PSIS_KEYS), R), dtype=torch.float64, device=x.device)
+        self._check(self.lib.tphu_psis(self._stream(x), x.data_ptr(), ones.data_ptr(), n, R, tail, out.data_ptr(), scratch.data_ptr(),
+                                       words, tile, slab, *self._data()), "tphu_psis")
+        res = {k: v.copy() for k, v in zip(PSIS_KEYS, out.cpu().numpy())}
+        res.update(tail_len=tail, n_rows=n, k_threshold=psis_k_threshold(n), totals=psis_totals(res, psis_k_threshold(n)))
         return res
 
     # ------------------------------------------------------------------------------ fused MCMC step

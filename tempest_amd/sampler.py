@@ -155,12 +155,19 @@ class Sampler:
         return self._core.compute_replicated(quantiles=quantiles, seed=seed, trim_importance_weights=trim_importance_weights,
                                              ess_trim=ess_trim, bins_trim=bins_trim)
 
-    def pointwise(self, trim_importance_weights: bool = True, ess_trim: float = 0.99, bins_trim: int = 1000) -> dict:
+    def pointwise(self, trim_importance_weights: bool = True, ess_trim: float = 0.99, bins_trim: int = 1000,
+                  psis_draws: Optional[int] = None, seed: Optional[int] = None) -> dict:
         """Pointwise log predictive densities of a HipCallbacks term-form source built with pointwise=True, over the weighted rows
         posterior() returns: {"lppd", "mean", "p_waic", "elpd_waic", "elpd_loo", "ess_loo": (n_terms,), "n_rows", "ess", "totals"},
         NumPy (HipCallbacks.pointwise).  The rows stay on the device; nothing of size rows x n_terms is formed.  Not available on a
-        sharded run (NotImplementedError)."""
-        return self._core.compute_pointwise(trim_importance_weights=trim_importance_weights, ess_trim=ess_trim, bins_trim=bins_trim)
+        sharded run (NotImplementedError).
+
+        A source built with pointwise="psis" adds "pareto_k", "elpd_psis", "ess_psis" (n_terms,) and, in "totals", elpd_psis,
+        elpd_psis_se, p_psis = lppd - elpd_psis, n_high_k and k_threshold (HipCallbacks.psis_loo).  Pareto smoothing is defined for
+        equally weighted rows: psis_draws of them (None: as many as there are weighted rows) are drawn from the weighted ones by
+        systematic resampling on the device, at the offset `seed` gives (None: the run's seed) -- the same seed, the same bits."""
+        return self._core.compute_pointwise(trim_importance_weights=trim_importance_weights, ess_trim=ess_trim, bins_trim=bins_trim,
+                                            psis_draws=psis_draws, seed=seed)
 
     def marginals(self, bins: int = 64, range=None, quantiles=(0.025, 0.16, 0.5, 0.84, 0.975), pairs=None, bins_2d: int = 32,
                   derived: bool = True, trim_importance_weights: bool = True, ess_trim: float = 0.99, bins_trim: int = 1000) -> dict:

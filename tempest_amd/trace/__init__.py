@@ -183,7 +183,7 @@ def trace_callbacks(prior_transform, log_likelihood, n_dim, derived=None, check=
     length or rows) the second callable is the TERM function (x, D) -> (n, n_terms), one column per observation, and the library owns
     the sum; without it, log_likelihood(x, D) -> (n,) may read elements D[name][j] only.  predict= (x, D) -> (n, n_predict) with
     n_predict= becomes the source's predict() (predict= without data= is refused: every column would have to be spelled out); pointwise=
-    as in HipCallbacks.  A 1-D entry as long as the term axis is a value per term, used whole; a 2-D entry (T, k) gives columns
+    as in HipCallbacks (True, or "psis" for psis_loo as well).  A 1-D entry as long as the term axis is a value per term, used whole; a 2-D entry (T, k) gives columns
     D[name][:, j] and xs @ D[name].T; constant integer indices read an element of any entry.
 
     replicate= (x, D, g) -> (n, n_replicate) with n_replicate= (as n_predict=) becomes the source's replicate(): one replicated
@@ -221,7 +221,8 @@ def trace_callbacks(prior_transform, log_likelihood, n_dim, derived=None, check=
                                           noise=c.args == "x, D, g", yarg=c.args == "x, y, D")
     source = emit_source(graphs, tables)
     n_derived = max(1, len(graphs["derived"].outputs)) if derived is not None else None
-    data_kwargs = {} if data is None else {"data": host, "n_terms": n_terms, "n_predict": n_predict, "pointwise": bool(pointwise)}
+    data_kwargs = {} if data is None else {"data": host, "n_terms": n_terms, "n_predict": n_predict,
+                                                 "pointwise": pointwise if isinstance(pointwise, str) else bool(pointwise)}
     if replicate is not None:
         data_kwargs.update(n_replicate=n_replicate, observed=observed)
     try:

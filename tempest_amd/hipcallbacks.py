@@ -210,21 +210,33 @@ def _row_blocks(n: int) -> int:
     return -(-n // (PREDICT_SUM_LAYOUT[0] * PREDICT_SUM_LAYOUT[1]))
 
 
+def _batched_words(fixed: int, per_r: int, count: int, cap: int) -> int:
+    """8-byte words of a driver's scratch: its `fixed` words and `per_r` for each index of a batch -- all `count` indices, or as many as
+    `cap` words hold (one at least).  The plugin's drivers divide what they get by the same two numbers (tphu_plan)."""
+    return fixed + per_r * min(count, max(1, cap // per_r))
+
+
+def _halved_tile(n: int, count: int, max_tile: int, min_workgroups: int) -> int:
+    """Indices per workgroup of a sweep over row blocks x index tiles: halved from max_tile while the grid has fewer workgroups than
+    min_workgroups."""
+    n_blocks, tile = _row_blocks(n), max_tile
+    while tile > 1 and n_blocks * -(-count // tile) < min_workgroups:
+        tile //= 2
+    return tile
+
+
 def replicate_scratch_words(n: int, n_replicate: int, n_q: int) -> int:
     """8-byte words of scratch tphu_replicated gets for this call: W, the block sums of w, sum k, the p-value count, the PIT counters,
     the chunk and block sums of u T, and for a batch of indices what predictive() keeps -- all n_replicate indices, or as many as
     PREDICT_SCRATCH_WORDS hold."""
     n_blocks = _row_blocks(n)
-    per_r = n_blocks + 258 * n_q + 1
-    return 3 + 3 * n_blocks + 3 * n_replicate + 2 * -(-n // PREDICT_SUM_LAYOUT[0]) + per_r * min(n_replicate, max(1, PREDICT_SCRATCH_WORDS // per_r))
+    return _batched_words(3 + 3 * n_blocks + 3 * n_replicate + 2 * -(-n // PREDICT_SUM_LAYOUT[0]), n_blocks + 258 * n_q + 1, n_replicate,
+                          PREDICT_SCRATCH_WORDS)
 
 
 def predict_tiles(n: int, n_predict: int, n_q: int):
     """(indices per workgroup, rows per workgroup of the select) predictive() launches with: the rule of PREDICT_MIN_WORKGROUPS."""
-    n_blocks = _row_blocks(n)
-    tile = PREDICT_MAX_TILE
-    while tile > 1 and n_blocks * -(-n_predict // tile) < PREDICT_MIN_WORKGROUPS:
-        tile //= 2
+    tile = _halved_tile(n, n_predict, PREDICT_MAX_TILE, PREDICT_MIN_WORKGROUPS)
     rts = max(1, min(tile, PREDICT_TABLES // max(1, n_q)))
     slabs = max(1, min(-(-n // 256), -(-PREDICT_MIN_WORKGROUPS // -(-n_predict // rts))))
     return tile, max(256, -(-(-(-n // slabs)) // 256) * 256, -(-(-(-n // 65535)) // 256) * 256)
@@ -234,25 +246,19 @@ def predict_scratch_words(n: int, n_predict: int, n_q: int) -> int:
     """8-byte words of scratch tphu_predictive gets for this call: W and the block sums of w, and for a batch of indices the block
     sums, bucket totals, prefixes, targets and NaN flags -- all n_predict indices, or as many as PREDICT_SCRATCH_WORDS hold."""
     n_blocks = _row_blocks(n)
-    per_r = n_blocks + 258 * n_q + 1
-    return 1 + n_blocks + per_r * min(n_predict, max(1, PREDICT_SCRATCH_WORDS // per_r))
+    return _batched_words(1 + n_blocks, n_blocks + 258 * n_q + 1, n_predict, PREDICT_SCRATCH_WORDS)
 
 
 def pointwise_tiles(n: int, n_terms: int) -> int:
     """Indices per workgroup pointwise() launches with: the rule of POINTWISE_MIN_WORKGROUPS."""
-    n_blocks = _row_blocks(n)
-    tile = POINTWISE_MAX_TILE
-    while tile > 1 and n_blocks * -(-n_terms // tile) < POINTWISE_MIN_WORKGROUPS:
-        tile //= 2
-    return tile
+    return _halved_tile(n, n_terms, POINTWISE_MAX_TILE, POINTWISE_MIN_WORKGROUPS)
 
 
 def pointwise_scratch_words(n: int, n_terms: int) -> int:
     """8-byte words of scratch tphu_pointwise gets for this call: W and the block sums of w, and for a batch of indices four arrays
     of block values and the two shifts -- all n_terms indices, or as many as POINTWISE_SCRATCH_WORDS hold."""
     n_blocks = _row_blocks(n)
-    per_r = 4 * n_blocks + 2
-    return 1 + n_blocks + per_r * min(n_terms, max(1, POINTWISE_SCRATCH_WORDS // per_r))
+    return _batched_words(1 + n_blocks, 4 * n_blocks + 2, n_terms, POINTWISE_SCRATCH_WORDS)
 
 
 def psis_tail_len(n: int) -> int:
@@ -270,10 +276,8 @@ def psis_scratch_words(n: int, n_terms: int) -> int:
     """8-byte words of scratch tphu_psis gets for this call: W and the block sums of w, and for a batch of indices the bucket totals,
     prefix, target, NaN flag, slot counter, cut, mean and the two shifts (264 words), three arrays of block values and the tail's M
     slots -- all n_terms indices, or as many as PSIS_SCRATCH_WORDS hold."""
-    n_blocks = _row_blocks(n)
-    tail = psis_tail_len(n)
-    per_r = 3 * n_blocks + 264 + (tail if tail >= PSIS_MIN_TAIL else 0)
-    return 1 + n_blocks + per_r * min(n_terms, max(1, PSIS_SCRATCH_WORDS // per_r))
+    n_blocks, tail = _row_blocks(n), psis_tail_len(n)
+    return _batched_words(1 + n_blocks, 3 * n_blocks + 264 + (tail if tail >= PSIS_MIN_TAIL else 0), n_terms, PSIS_SCRATCH_WORDS)
 
 
 def compare_pointwise(a, b, key="elpd_loo"):
@@ -431,8 +435,11 @@ class _Parts(namedtuple("_Parts", "tables term n_derived predict pointwise repli
     def text(self, source: str) -> str:
         """The translation unit for `source`."""
         # lines of one part only are dropped whole without it; //@D: the data form; //@Q: what predict, pointwise and replicate share --
-        # the layout constants, the row loads, the sum of the weights; //@S: what predict, replicate and psis share -- the fold of the block
-        # sums, the select's key and its narrowing kernel; //@R: the helpers a traced source calls
+        # the layout constants, the row loads, the sum of the weights, and on the host the batch plan, the scratch carver and the weight
+        # sum of their drivers; //@S: what predict, replicate and psis share -- the ONE body of the moment kernels and of the select's
+        # pass (the parts' kernels of those names are wrappers that hand it their row value), the fold of the block sums, the select's key
+        # and its narrowing kernel, and on the host the quantile check, the moment pair and the select loop; //@R: the helpers a traced
+        # source calls
         rows = self.predict or self.pointwise or self.replicate
         keep = {"//@D": self.tables is not None, "//@S": self.predict or self.replicate or self.psis, "//@Q": rows, "//@R": self.traced}
         keep.update((part.mark, bool(getattr(self, part.name))) for part in _PARTS if part.mark)

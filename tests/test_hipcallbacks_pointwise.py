@@ -153,14 +153,15 @@ def all_cases():
 
 
 # ------------------------------------------------------------------------------------------------- CPU
-# What the parent of this feature (6ed21b6) generated for three predict-form sources: SHA-256 of the text and the file name
-# build_plugin gave it under the recorded environment (PARENT_ENV)
+# Three predict-form sources: SHA-256 of the text -- recorded again when the moment and select kernels became wrappers of one shared
+# body each, which moved every text with predict() in it and none without -- and the file name build_plugin gave the parent of this
+# feature (6ed21b6) under the recorded environment (PARENT_ENV), hashed from the text of that time
 def parent_predict_cases():
     return (   # source, n_dim, tables, term, n_derived, text hash, file name
-        (BASE + PRED_X, 3, None, False, 0, "2a095f25ebab5757d1ee51a31e4ef5c3488a222380b65e307bdee005f5039008", "tphu_3d_343e121977ab325cfa63.so"),
-        (TERM_D + PRED_D, 3, (("t", 1),), True, 0, "dfc4a66c805c86f19faa1016425b8d19c924fc7592aeb7858cfebef34c6f9d67",
+        (BASE + PRED_X, 3, None, False, 0, "eac1200fb0927cbe343b57a12f63e7adb4ee88f4850b708436d46937e6c6640b", "tphu_3d_343e121977ab325cfa63.so"),
+        (TERM_D + PRED_D, 3, (("t", 1),), True, 0, "acbad4f4d592ba6c67c06021f7c73124a1830cfb3623b94bdfa928359a4bc8ec",
          "tphu_3d_ed63f11797bfe745fab2.so"),
-        (BASE + DERIVED + PRED_X, 4, None, False, 1, "2a949cc4ab713ea691a8c0fe0a4a42edec9280452d6a210f76fc19875788b6dc",
+        (BASE + DERIVED + PRED_X, 4, None, False, 1, "0cd3236e6c8e5d05fd83f30812f7de48660ed9e6d76c0068e3a7c982dce70417",
          "tphu_4d_2a0630f7e195a2552641.so"),
     )
 

@@ -7,6 +7,7 @@ without any copy.  backend="torch" hands torch-ROCm tensors to the callbacks (no
 backend="numpy" stages through the host for NumPy likelihoods (drop-in, PCIe-bound), "auto" probes.
 """
 import warnings
+from collections import namedtuple
 from pathlib import Path
 from typing import Optional, Union
 
@@ -144,6 +145,9 @@ def _pack_blobs(rows, dtype=None):
     shape = arr.shape[:1] + tuple(m for m in arr.shape[1:] if m != 1)
     return arr if shape == arr.shape else arr.reshape(shape)
 
+
+_Selection = namedtuple("_Selection", "w_dev sel m_sel wdiv m s1")       # SamplerCore._select
+_Derived = namedtuple("_Derived", "fn on_device width")                  # SamplerCore._derived_source
 
 class SamplerCore:
     """Internal coordinator; `Sampler` delegates to it (core.py:20-108)."""
@@ -295,78 +299,69 @@ class SamplerCore:
         return ess < getattr(self, "n_total", 0)
 
     # ------------------------------------------------------------------------------ outputs
-    def compute_posterior(self, resample=False, return_blobs=False, trim_importance_weights=True, return_logw=False,
-                          ess_trim=0.99, bins_trim=1000):
-        """Weighted posterior samples from the whole history (core.py:187-242)."""
-        import torch
+    def _select(self, trim_importance_weights, ess_trim, bins_trim):
+        """The history rows a result uses, on this shard: a _Selection of the device weights at beta = 1 (w_dev), the device indices of
+        the kept rows (sel; None: the first m_sel), their number and what their weights are divided by (wdiv), and the (m, s1) of the
+        reweighting pass -- from the trim threshold and the compaction, both on the device.  On a sharded run the threshold is a
+        statistic of the GLOBAL weight distribution, which the library finds without moving the weights
+        (tph_trim_threshold_global), and the weights are already normalised by the global sum; m_sel is this shard's share of the
+        kept rows, counted here, and a shard that keeps none has sel None."""
         st = self.state
         ctx = st.ctx
         ctx.use_current_stream()
         m, s1, _ = st.reweight_eval([1.0])[0]
-        nh = st.n_history_global()
         w_dev = ctx.weights(1.0, m, s1)
+        sel, m_sel, wdiv = None, ctx.size, 1.0
+        if trim_importance_weights:
+            sharded = st.comm is not None and st.comm.active
+            thr_dev, out = ctx.trim_threshold(w_dev, ess_trim, bins_trim, sync=True, global_=sharded)
+            wdiv = float(out[1])
+            m_sel = int((w_dev >= thr_dev[0]).sum().item()) if sharded else int(out[2])
+            sel = ctx.compact_indices(w_dev, thr_dev[0:1], m_sel) if m_sel else None
+        return _Selection(w_dev, sel, m_sel, wdiv, m, s1)
+
+    def compute_posterior(self, resample=False, return_blobs=False, trim_importance_weights=True, return_logw=False,
+                          ess_trim=0.99, bins_trim=1000):
+        """Weighted posterior samples from the whole history (core.py:187-242): select, gather the rows, attach their blobs, on a
+        sharded run gather the ranks' parts (every rank returns the posterior over the WHOLE history: rows of all shards, rank
+        order), resample.  Threshold, compaction and the gather into row-major (M, d) stay on the device; only the kept rows
+        cross PCIe or travel between ranks."""
+        import torch
+        from .tools import systematic_draw
+        st = self.state
+        ctx = st.ctx
+        comm = st.comm if (st.comm is not None and st.comm.active) else None
+        s = self._select(trim_importance_weights, ess_trim, bins_trim)
+        sel, m_sel = s.sel, s.m_sel
         logw = None
         if return_logw:       # the untrimmed, normalised log-weights (core.py:233-242)
-            logw = ctx.logw(1.0, nh).cpu().numpy() - (float(m + np.log(s1)) + np.log(nh))
-        comm = st.comm
+            nh = st.n_history_global()
+            logw = ctx.logw(1.0, nh).cpu().numpy() - (float(s.m + np.log(s.s1)) + np.log(nh))
+        x_dev, logl_dev, w_sel = ctx.posterior_rows(sel, m_sel, w=s.w_dev, wdiv=s.wdiv)
+        if resample and comm is None:
+            # one shard: the draw composes with the selection on the device and the rows are gathered once more
+            pick = systematic_draw(ctx, w_sel, m_sel, np.random.random())
+            sel = pick if sel is None else ctx.index_compose(sel, pick)
+            x_dev, logl_dev, w_sel = ctx.posterior_rows(sel, m_sel)
         blobs = st.get_history("blobs", flat=True) if (self.config.blobs_dtype is not None and st._blobs) else None
-        # derived quantities: pure functions of x, evaluated on the rows this call returns while they are on the device
+        # derived quantities: pure functions of x, evaluated on the rows this call returns while they are on the device (a rank
+        # with no kept rows: an empty (0, k) block)
         derive = self._derived_fn() if (return_blobs and blobs is None) else None
-        if comm is None or not comm.active:
-            # single shard: threshold, compaction, resampling and the gather into row-major (M, d) stay on the device;
-            # only the M returned rows cross PCIe
-            sel, m_sel, wdiv = self._select_rows(w_dev, trim_importance_weights, ess_trim, bins_trim)
-            if resample:
-                from .tools import SQRTEPS
-                _, _, w_sel = ctx.posterior_rows(sel, m_sel, w=w_dev, wdiv=wdiv)
-                cdf = ctx.cdf(w_sel)
-                tot = float(cdf[-1].item())
-                pick = ctx.resample_systematic(cdf, m_sel, np.random.random(),
-                                               renorm=tot if abs(tot - 1.0) > SQRTEPS else 1.0)
-                sel = pick if sel is None else ctx.index_compose(sel, pick)
-                x_dev, logl_dev, _ = ctx.posterior_rows(sel, m_sel)
-                weights = np.ones(m_sel) / m_sel
-            else:
-                x_dev, logl_dev, w_sel = ctx.posterior_rows(sel, m_sel, w=w_dev, wdiv=wdiv)
-                weights = w_sel.cpu().numpy()
-            if derive is not None:
-                blobs = derive(x_dev)
-            x, logl = x_dev.cpu().numpy(), logl_dev.cpu().numpy()
-            if blobs is not None and derive is None and sel is not None:
-                blobs = blobs[sel.cpu().numpy()]
-        else:
-            # sharded run: every rank returns the posterior over the WHOLE history (rows of all shards, rank order).
-            # The trim threshold is a statistic of the global weight distribution: the library finds it without moving
-            # the weights (tph_trim_threshold_global); every shard then compacts and gathers its own kept rows on the
-            # device and only those rows travel.  The weights are already normalised by the global sum.
-            if logw is not None:
-                logw = comm.gather_rows(logw)
-            sel, m_sel, wdiv = None, ctx.size, 1.0
-            if trim_importance_weights:
-                thr_dev, out = ctx.trim_threshold(w_dev, ess_trim, bins_trim, sync=True, global_=True)
-                wdiv = float(out[1])
-                m_sel = int((w_dev >= thr_dev[0]).sum().item())      # this shard's share of the kept rows
-                sel = ctx.compact_indices(w_dev, thr_dev[0:1], m_sel) if m_sel else None
-            if m_sel:
-                x_dev, logl_dev, w_sel = ctx.posterior_rows(sel, m_sel, w=w_dev, wdiv=wdiv)
-                x, logl, weights = x_dev.cpu().numpy(), logl_dev.cpu().numpy(), w_sel.cpu().numpy()
-            else:
-                x_dev = torch.empty((0, st.n_dim), dtype=torch.float64, device=ctx.device)
-                x, logl, weights = np.empty((0, st.n_dim)), np.empty(0), np.empty(0)
-            if derive is not None:               # this rank's kept rows (none: an empty (0, k) block), gathered like x below
-                blobs = derive(x_dev)
-            elif blobs is not None and sel is not None:
-                blobs = blobs[sel.cpu().numpy()]
+        if derive is not None:
+            blobs = derive(x_dev)
+        elif blobs is not None and sel is not None:
+            blobs = blobs[sel.cpu().numpy()]
+        x, logl = x_dev.cpu().numpy(), logl_dev.cpu().numpy()
+        weights = np.ones(m_sel) / m_sel if w_sel is None else w_sel.cpu().numpy()
+        if comm is not None:
             x, logl, weights = comm.gather_rows(x), comm.gather_rows(logl), comm.gather_rows(weights)
             if blobs is not None:
                 blobs = comm.gather_rows(blobs)
-            if resample:
-                from .tools import SQRTEPS
+            if logw is not None:
+                logw = comm.gather_rows(logw)
+            if resample:      # on the gathered host rows; the total is NumPy's sum of the gathered weights
                 wt = torch.from_numpy(np.ascontiguousarray(weights)).to(ctx.device)
-                cdf = ctx.cdf(wt)
-                tot = float(weights.sum())
-                idx = ctx.resample_systematic(cdf, len(weights), np.random.random(),
-                                              renorm=tot if abs(tot - 1.0) > SQRTEPS else 1.0).cpu().numpy()
+                idx = systematic_draw(ctx, wt, len(weights), np.random.random(), total=float(weights.sum())).cpu().numpy()
                 x, logl = x[idx], logl[idx]
                 if blobs is not None:
                     blobs = blobs[idx]
@@ -380,17 +375,6 @@ class SamplerCore:
             out.append(logw)
         return tuple(out)
 
-    def _select_rows(self, w_dev, trim_importance_weights, ess_trim, bins_trim):
-        """One shard: (sel, m_sel, wdiv) -- the device indices of the rows the posterior keeps (None: all of them), how many, and
-        what their weights are divided by -- from the trim threshold and the compaction, both on the device."""
-        ctx = self.state.ctx
-        sel, m_sel, wdiv = None, ctx.size, 1.0
-        if trim_importance_weights:
-            thr_dev, out = ctx.trim_threshold(w_dev, ess_trim, bins_trim, sync=True)
-            m_sel, wdiv = int(out[2]), float(out[1])
-            sel = ctx.compact_indices(w_dev, thr_dev[0:1], m_sel)
-        return sel, m_sel, wdiv
-
     def _hip_owner(self, what, has, needs):
         """The HipCallbacks object the likelihood belongs to, with the optional part Sampler.`what` reduces over: refused otherwise."""
         from ._lib import TempestHipError
@@ -401,22 +385,24 @@ class SamplerCore:
         return owner
 
     def _weighted_rows(self, what, unbuilt, trim_importance_weights, ess_trim, bins_trim, owner=None, with_sel=False):
-        """(x_dev, w_sel): the rows and weights compute_posterior returns (same selection and row order), left on the device -- for
-        `owner`, a HipCallbacks object, on its device; with_sel: (x_dev, w_sel, sel), sel their device indices into the history (None:
+        """(x_dev, w_sel): the rows and weights compute_posterior returns (same selection and row order: the same _select and
+        posterior_rows call), left on the device -- for `owner`, a HipCallbacks object, on its device; with_sel: (x_dev, w_sel, sel), sel their device indices into the history (None:
         its first rows).  One shard only: Sampler.`what` needs `unbuilt` to fold the ranks' parts."""
         st = self.state
         if st.comm is not None and st.comm.active:
             raise NotImplementedError(f"Sampler.{what} is not available on a sharded run yet: every rank holds a part of the rows, and "
                                       f"{unbuilt} (DESIGN.md section 10)")
-        ctx = st.ctx
-        ctx.use_current_stream()
-        if owner is not None and owner.device is None:
-            owner.device = st.device
-        m, s1, _ = st.reweight_eval([1.0])[0]
-        w_dev = ctx.weights(1.0, m, s1)
-        sel, m_sel, wdiv = self._select_rows(w_dev, trim_importance_weights, ess_trim, bins_trim)
-        x_dev, _, w_sel = ctx.posterior_rows(sel, m_sel, w=w_dev, wdiv=wdiv)
-        return (x_dev, w_sel, sel) if with_sel else (x_dev, w_sel)
+        if owner is not None:
+            self._with_device(owner)
+        s = self._select(trim_importance_weights, ess_trim, bins_trim)
+        x_dev, _, w_sel = st.ctx.posterior_rows(s.sel, s.m_sel, w=s.w_dev, wdiv=s.wdiv)
+        return (x_dev, w_sel, s.sel) if with_sel else (x_dev, w_sel)
+
+    def _with_device(self, hc):
+        """`hc`, a HipCallbacks object, on this run's device if it has none yet."""
+        if hc.device is None:
+            hc.device = self.state.device
+        return hc
 
     def compute_predictive(self, quantiles=(0.025, 0.5, 0.975), trim_importance_weights=True, ess_trim=0.99, bins_trim=1000):
         """Posterior predictive mean, variance and quantiles of the HipCallbacks source's predict(x, r) over the rows and weights
@@ -451,15 +437,13 @@ class SamplerCore:
         res = owner.pointwise(x_dev, w_sel)
         if owner.psis_enabled:
             from .hipcallbacks import PSIS_KEYS
-            from .tools import SQRTEPS
+            from .tools import systematic_draw
             n_draws = x_dev.shape[0] if psis_draws is None else psis_draws
             if isinstance(n_draws, bool) or not isinstance(n_draws, (int, np.integer)) or int(n_draws) <= 0:
                 raise ValueError(f"Sampler.pointwise: psis_draws must be a positive int, got {psis_draws!r}")
             ctx = self.state.ctx
-            cdf = ctx.cdf(w_sel)
-            tot = float(cdf[-1].item())
             u0 = float(np.random.default_rng(self.rng.seed if seed is None else seed).random())
-            pick = ctx.resample_systematic(cdf, int(n_draws), u0, renorm=tot if abs(tot - 1.0) > SQRTEPS else 1.0)
+            pick = systematic_draw(ctx, w_sel, int(n_draws), u0)
             rows, _, _ = ctx.posterior_rows(pick if sel is None else ctx.index_compose(sel, pick), int(n_draws))
             self._psis_rows = rows
             ps = owner.psis_loo(rows)
@@ -473,21 +457,15 @@ class SamplerCore:
         quantities -- over the rows and weights compute_posterior returns (same selection, on the device): the rows stay there,
         only per-column arrays and the tables reach the host (HipContext.marginals)."""
         import torch
-        from .hipcallbacks import HipCallbacks
         x_dev, w_sel = self._weighted_rows("marginals", "folding per-rank minima, maxima, block sums and tables is not built",
                                            trim_importance_weights, ess_trim, bins_trim)
         n_dim, n_derived = x_dev.shape[1], 0
-        fn = self.config.derived if derived else None
-        owner = getattr(self.config.log_likelihood, "__self__", None)
-        if derived and fn is None and isinstance(owner, HipCallbacks) and owner.n_derived > 0:
-            fn = owner.derived
-        if fn is not None:
-            if isinstance(getattr(fn, "__self__", None), HipCallbacks):      # evaluated where the rows are
-                if fn.__self__.device is None:
-                    fn.__self__.device = self.state.device
-                extra = fn(x_dev)
-            else:                                                            # a host function: its (M, k) block is uploaded
-                extra = torch.from_numpy(self._derived_fn()(x_dev)).to(x_dev.device)
+        src = self._derived_source() if derived else None
+        if src is not None:
+            if src.width is not None:        # a plugin's columns: evaluated where the rows are, and left there
+                extra = src.fn(x_dev)
+            else:                            # a user's function: its host (M, k) block is uploaded
+                extra = torch.from_numpy(self._derived_fn(src)(x_dev)).to(x_dev.device)
             extra = extra.to(torch.float64).reshape(x_dev.shape[0], -1)
             n_derived = extra.shape[1]
             x_dev = torch.cat([x_dev, extra], dim=1).contiguous()
@@ -495,10 +473,10 @@ class SamplerCore:
         out.update(n_dim=int(n_dim), n_derived=int(n_derived))
         return out
 
-    def _derived_fn(self):
-        """rows (M, d) on the device -> the derived quantities as a host (M, k) float64 array, or None without a derived function:
-        config.derived, else the `derived` of the HipCallbacks object the likelihood belongs to."""
-        import torch
+    def _derived_source(self):
+        """Where the derived quantities come from -- config.derived, else the `derived` of the HipCallbacks object the likelihood
+        belongs to -- as a _Derived: fn, on_device (fn takes the device rows; else their host copy) and width (a plugin's column
+        count, known without a call; None for a user's function).  None without a derived function."""
         from .hipcallbacks import HipCallbacks
         fn = self.config.derived
         owner = getattr(self.config.log_likelihood, "__self__", None)
@@ -506,18 +484,26 @@ class SamplerCore:
             fn = owner.derived
         if fn is None:
             return None
-        on_device = isinstance(getattr(fn, "__self__", None), HipCallbacks)
-        width = fn.__self__.n_derived if on_device else None      # a plugin's width is known without a call
-        if on_device:
-            if fn.__self__.device is None:
-                fn.__self__.device = self.state.device
-        elif self.config.backend == "auto":
+        plugin = getattr(fn, "__self__", None)
+        if isinstance(plugin, HipCallbacks):
+            return _Derived(fn, True, self._with_device(plugin).n_derived)
+        backend = self.config.backend
+        if backend == "auto":
             self._ensure_callbacks()
             if self.callbacks.backend is None:
                 self.callbacks._probe()
-            on_device = self.callbacks.backend == "torch"
-        else:
-            on_device = self.config.backend == "torch"
+            backend = self.callbacks.backend
+        return _Derived(fn, backend == "torch", None)
+
+    def _derived_fn(self, src=None):
+        """rows (M, d) on the device -> the derived quantities of _derived_source (`src`, if the caller has it) as a host (M, k)
+        float64 array, or None without a derived function."""
+        import torch
+        if src is None:
+            src = self._derived_source()
+        if src is None:
+            return None
+        fn, on_device, width = src
 
         def run(x_dev):
             m = x_dev.shape[0]

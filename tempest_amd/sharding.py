@@ -24,7 +24,7 @@ def resample_sharded(state, w, scheme, rng, n_local):
     import torch
     from .device import TAG_RESAMPLE, TAG_SYST
     from ._philox_host import uniform_scalar
-    from .tools import SQRTEPS
+    from .tools import renorm_total
     ctx, comm = state.ctx, state.comm
     G, me, d = comm.world_size, comm.rank, state.n_dim
     n_slots = n_local * G
@@ -35,8 +35,7 @@ def resample_sharded(state, w, scheme, rng, n_local):
     else:
         cdf, tot = ctx.cdf_global(w, total=True)
         u0 = uniform_scalar(rng.seed, tick, TAG_SYST)
-        idx = ctx.resample_select_global(cdf, n_slots, 1, rng.seed, tick, u0=u0,
-                                         pscale=tot if abs(tot - 1.0) > SQRTEPS else 1.0, tag=TAG_RESAMPLE)
+        idx = ctx.resample_select_global(cdf, n_slots, 1, rng.seed, tick, u0=u0, pscale=renorm_total(tot), tag=TAG_RESAMPLE)
     if ctx.p2p_active:
         # ranks of one node: every holder writes its rows straight into the slot owner's window over the peer mapping
         # (tph_resample_put_global) -- no counts, no packing, no all-to-all, no host synchronisation

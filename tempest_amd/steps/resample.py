@@ -51,17 +51,12 @@ class Resampler:
             from ..sharding import resample_sharded
             u, x, logl = resample_sharded(st, w, self.resample, rng, n)
         else:
-            cdf = ctx.cdf(w)
             if self.resample == "mult":
-                idx = ctx.resample_multinomial(cdf, n, rng.seed, rng.next())
-            else:
-                # tools.py:214-217: renormalise when |sum w - 1| > sqrt(eps); one uniform for the whole comb
-                from ..tools import SQRTEPS
+                idx = ctx.resample_multinomial(ctx.cdf(w), n, rng.seed, rng.next())
+            else:                    # one uniform for the whole comb
+                from ..tools import systematic_draw
                 from ..device import TAG_SYST
-                tot = float(cdf[-1].item())
-                renorm = tot if abs(tot - 1.0) > SQRTEPS else 1.0
-                u0 = _host_uniform(rng, TAG_SYST)
-                idx = ctx.resample_systematic(cdf, n, u0, renorm=renorm)
+                idx = systematic_draw(ctx, w, n, _host_uniform(rng, TAG_SYST))
             d = st.n_dim
             u, x, logl = ctx.empty(d, n), ctx.empty(d, n), ctx.empty(n)
             ctx.gather(idx, u, x, logl)

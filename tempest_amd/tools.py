@@ -107,12 +107,21 @@ def systematic_resample(size: int, weights: np.ndarray, random_state: Optional[i
     if random_state is not None:
         np.random.seed(random_state)
     w = np.asarray(weights, dtype=np.float64)
-    tot = float(np.sum(w))
-    renorm = tot if abs(tot - 1.0) > SQRTEPS else 1.0
-    u0 = np.random.random()
     c = _ctx()
-    cdf = c.cdf(_to_dev(w, c))
-    return c.resample_systematic(cdf, int(size), u0, renorm=renorm).cpu().numpy()
+    return systematic_draw(c, _to_dev(w, c), int(size), np.random.random(), total=float(np.sum(w))).cpu().numpy()
+
+
+def renorm_total(tot: float) -> float:
+    """What the comb's positions are scaled by (tools.py:214-217): the weights' total where |total - 1| > sqrt(eps), else 1."""
+    return tot if abs(tot - 1.0) > SQRTEPS else 1.0
+
+
+def systematic_draw(ctx, w_dev, n_out: int, u0: float, total: Optional[float] = None):
+    """Device indices (int64, n_out) of the systematic draw at the offset u0 from the device weights w_dev, renormalised by
+    renorm_total.  total None: the last cumulative weight, read from the device (one host wait); else the caller's own sum."""
+    cdf = ctx.cdf(w_dev)
+    tot = float(cdf[-1].item()) if total is None else total
+    return ctx.resample_systematic(cdf, n_out, u0, renorm=renorm_total(tot))
 
 
 class ProgressBar:
